@@ -12,7 +12,11 @@ bounds, RK update), inputs resident in HBM.
 Workload (config.workload): BASELINE.json configs[1] -- 3D periodic-cube remap (problem 10,
 Taylor-Green mesh motion, erfc bump), p = 3, -pa -ho 3 -lo 5 -fct 2 (the combination the reference
 itself allows on a device, remhos.cpp:391-397), refined to --rs levels (default 5: 884 736 hex,
-56.6 M dofs).  At N = 1 the same JSON line carries a "p6" block: BASELINE.json configs[2]
+56.6 M dofs).  A plain run does only that: set-up, W warm-up steps, K timed steps, the JSON line.  `--full` adds
+everything else this file measures and checks (the blocks below, `mass_check`, `cpu_baseline`, the strong leg and
+one-block mass check of N > 1).  `--dump-outputs DIR` writes what the timed run computed (`dump_outputs`).
+
+With `--full`, at N = 1 the same JSON line carries a "p6" block: BASELINE.json configs[2]
 (periodic-cube -rs 4 -o 6, 37.9 M dofs), timed after the p = 3 region with the same K and W, a "transport" block (the
 same mesh with -p 0: the periodic behaviour the reference pins), an "lo4" block (the p = 3 and p = 6 workloads with
 the subcell residual-distribution LO solver, -lo 4, inside the stage kernel) and a "sustained" block (the p = 3 workload
@@ -33,7 +37,7 @@ process, before anything in this process touches the GPU).
 
 The LAST stdout line is the record: one compact JSON line (< 6 KB, numbers and short labels only, `compact_line`); the full result with every
 explanatory string goes to bench_detail.json (DESIGN.md 5 explains each field).  The line carries `roofline` for the dominant kernel (ho_kernel2<p, 1>, duration from HIP events
-on the kernel's own stream inside the timed region) and `cpu_baseline` (the C++/OpenMP CPU port of
+on the kernel's own stream inside the timed region) and, with `--full`, `cpu_baseline` (the C++/OpenMP CPU port of
 oracle/ timed on the host cores on a bounded sample of the same workload; rank 0 at N = 1 only).
 """
 import argparse
@@ -93,6 +97,36 @@ MASS_SOLVE = {  # name -> (rel_tol, abs_tol, max_iter, jacobi_step, constant_mod
     "reference": ((0.0, 1e-8, 100, 0, 0), "abs 1e-8 (reference)"),
     "roundoff-twin": ((1e-14, 0.0, 100, 0, 1), "rel 1e-14 + constant mode"),
 }
+
+
+DUMP_DOFS = 1 << 21  # dofs of the field that --dump-outputs writes (u + its indices: 2 x 16 MB in float64)
+DUMP_SEED = 20251016
+
+
+def dump_outputs(d, x, mass_max):
+    """--dump-outputs DIR: what the timed run computed in its last step, as float64 .npy files, for comparing two builds
+    output for output (the inputs depend only on the arguments).
+      u.npy        the field u after the last timed step (what Stepper.x hands its caller): all of it up to DUMP_DOFS dofs,
+                   else a fixed seeded sample of DUMP_DOFS dofs -- one uniformly drawn dof per stratum of n / DUMP_DOFS
+      u_index.npy  the E-vector indices of those dofs
+      mass_max.npy [final mass, max u] (the sanity figures of the line; at N > 1 the only output written: rank 0, reduced)"""
+    import numpy as np
+
+    os.makedirs(d, exist_ok=True)
+    if x is not None:
+        import torch
+
+        n = x.numel()
+        if n <= DUMP_DOFS:
+            idx = np.arange(n, dtype=np.int64)
+        else:
+            lo = np.arange(DUMP_DOFS, dtype=np.int64) * n // DUMP_DOFS
+            hi = np.arange(1, DUMP_DOFS + 1, dtype=np.int64) * n // DUMP_DOFS
+            idx = lo + (np.random.default_rng(DUMP_SEED).random(DUMP_DOFS) * (hi - lo)).astype(np.int64)
+        u = x.reshape(-1)[torch.from_numpy(idx).to(x.device)].cpu().numpy()
+        np.save(os.path.join(d, "u.npy"), u.astype(np.float64))
+        np.save(os.path.join(d, "u_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(d, "mass_max.npy"), np.asarray(mass_max, dtype=np.float64))
 
 
 COMPACT_LIMIT = 6144  # the driver keeps an ~8 KB tail of stdout: the final line must fit with room to spare
@@ -497,10 +531,12 @@ _CASES = {}
 
 
 def measure(args, lib, order, rs, world, rank, dev, dist, backend, with_counters=True, problem=None, mass_solve=None,
-            steps=None, warmup=None, smi_period=None, per_step=False, keep_state=False, lo=None, mesh=None, dt_scale=1.0):
+            steps=None, warmup=None, smi_period=None, per_step=False, keep_state=False, lo=None, mesh=None, dt_scale=1.0,
+            dump_dir=None):
     """Set up one configuration, time K steps after W warm-up steps, return the result fields.
     smi_period: sample rocm-smi from a host thread every so many seconds during the timed region (None: not at all --
-    the headline figure is measured without instrumentation); per_step: HIP events between the steps (first / steady)."""
+    the headline figure is measured without instrumentation); per_step: HIP events between the steps (first / steady);
+    dump_dir: write the state after the last timed step there (dump_outputs; rank 0, the field itself at N = 1 only)."""
     import torch
 
     from remhos_amd.case import Case, make_config
@@ -578,6 +614,8 @@ def measure(args, lib, order, rs, world, rank, dev, dist, backend, with_counters
         red = torch.tensor([umax], dtype=torch.float64, device=rdev)
         dist.all_reduce(red, op=dist.ReduceOp.MAX)
         umax = float(red[0])
+    if dump_dir and rank == 0:
+        dump_outputs(dump_dir, st.x if world == 1 else None, (mass, umax))
     one_kernel = st.one_kernel
     ne_owned, ndof, ne_global, n_lat = case.ne_owned, case.ndof, case.ne_global, list(case.n)
     xinfo = None
@@ -903,6 +941,12 @@ def main():
                          "(block `cpp_loop`; on by default in the full default run)")
     ap.add_argument("--py-loop", action="store_true",
                     help="N > 1: drive the stages from Python (remhos_amd/stepper.py over torch.distributed) instead of the C++ loop")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline: N = 1 the p6 / cube01_p4 / transport / sustained / lo4 / "
+                         "granular / configs0_2d / cpp_loop blocks, mass_check and cpu_baseline; N > 1 the strong leg and the one-block "
+                         "mass check (off: set-up, warm-up, the timed steps and the line only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what they computed to DIR/<name>.npy (float64): see dump_outputs")
     args = ap.parse_args()
     if args.gpus not in PART:
         raise SystemExit("--gpus must be 1, 2, 4 or 8")
@@ -931,7 +975,7 @@ def main():
         if one_gpu:
             if rank == 0:
                 out = measure_cpp_loop(args, lib, world, 0, 0, None)
-                if args.scaling == "weak" and not args.no_strong_leg:
+                if args.full and args.scaling == "weak" and not args.no_strong_leg:
                     a2 = copy.copy(args)
                     a2.scaling = "strong"
                     strong = measure_cpp_loop(a2, lib, world, 0, 0, None)
@@ -952,7 +996,7 @@ def main():
             if not all_ranks_ok(tag.replace("/", "_"), world, rank, out is not None):
                 rank_log(rank, "not every rank succeeded: all ranks take the Python loop")
                 out = None
-            if out is not None and args.scaling == "weak" and not args.no_strong_leg:
+            if out is not None and args.full and args.scaling == "weak" and not args.no_strong_leg:
                 # BASELINE configs[3] in the same line: the SAME -rs mesh box-partitioned over the ranks (a second communicator
                 # through its own id file; skipped as a whole unless every rank got through it)
                 a2 = copy.copy(args)
@@ -970,12 +1014,14 @@ def main():
                     "scaling": args.scaling, "vs_baseline": None, "dtype": "f64", "data": "synthetic",
                     "rccl_ranks": out["config"].get("comm_ranks")}
             line.update({k: v for k, v in out.items() if k not in ("value", "ms_per_step")})
-            # mass_check of an N > 1 line: the result of a partitioned run does not depend on the partition (tests/test_dist_gloo.py,
+            if args.dump_outputs:
+                dump_outputs(args.dump_outputs, None, (out["config"]["final_mass"], out["config"]["max_value"]))
+            # (--full) mass_check of an N > 1 line: the result of a partitioned run does not depend on the partition (tests/test_dist_gloo.py,
             # tests/test_gpu_exchange.py: bit-identical to one block), so rank 0 repeats a leg as ONE block with the same C++ loop and
             # compares the final masses -- the strong leg's mesh (the -rs mesh: always fits one GPU); the weak leg's too where it is
             # small enough to be set up on one GPU in seconds (validation runs; a full -rs 5 block per rank is not repeated)
             checks = {}
-            for leg_name, leg, leg_args in (("strong", strong, None), (args.scaling, out, args)):
+            for leg_name, leg, leg_args in (("strong", strong, None), (args.scaling, out, args)) if args.full else ():
                 if leg is None or leg_name in checks or leg["config"]["global_dofs"] > 80e6:
                     continue
                 a1 = copy.copy(args)
@@ -1025,9 +1071,9 @@ def main():
         backend = dist.get_backend()
 
     lib = bind_driver(load_library())
-    extras = world == 1 and not args.no_extras
+    extras = world == 1 and args.full and not args.no_extras
     main_res = measure(args, lib, args.order, args.rs, world, rank, dev, dist, backend, keep_state=extras,
-                       smi_period=0.05 if args.smi else None)
+                       smi_period=0.05 if args.smi else None, dump_dir=args.dump_outputs)
     default_case = (args.order, args.mesh, args.problem) == (3, "periodic-cube", 10)
 
     def verdict(mass_dev, twin_dev):
@@ -1095,7 +1141,7 @@ def main():
         main_res["mass_check"] = mass_check(main_res, args.order, args.rs)
     main_res.pop("_state", None)
     p6, transport, sustained, cube01_p4 = None, None, None, None
-    if world == 1 and default_case and not args.no_p6:
+    if world == 1 and args.full and default_case and not args.no_p6:
         p6 = measure(args, lib, 6, 4, world, rank, dev, dist, backend, keep_state=extras)
         if extras and args.mass_solve != "exact":
             p6["mass_check"] = mass_check(p6, 6, 4)
@@ -1197,7 +1243,7 @@ def main():
             out["configs0_2d"] = config0
         if cpp_loop is not None:
             out["cpp_loop"] = cpp_loop
-        if args.gpus == 1 and not args.no_cpu_baseline:
+        if args.gpus == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(lib, args.order, args.rs, args.mass_solve)
         emit(out, args.gpus)
     if dist is not None:

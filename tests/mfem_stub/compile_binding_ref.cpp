@@ -1,6 +1,6 @@
 // compile-only: the binding header behind the REFERENCE'S OWN interface headers (found through -I <reference checkout>; only
-// mfem.hpp and general/forall.hpp are the stubs of this directory) -- tests/test_binding_compiles.py, skipped where the reference
-// checkout is absent.  What the binding derives from and overrides is then what Remhos declares, not a restatement of it.
+// mfem.hpp and general/forall.hpp are the stubs of this directory) -- tools/check_reference_headers.py <checkout> (the checkout is not part
+// of this repository).  What the binding derives from and overrides is then what Remhos declares, not a restatement of it.
 #include "remhos_ho.hpp"
 #include "remhos_lo.hpp"
 #include "remhos_fct.hpp"

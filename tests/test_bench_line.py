@@ -109,3 +109,31 @@ def test_committed_traffic_entries_belong_to_the_committed_kernel_sources():
     assert stage, "no stage entries"
     for k, v in stage.items():
         assert v["kernel_src_sha"] == have, (k, v["kernel_src_sha"], have)
+
+
+def test_dump_outputs_sample_is_fixed_and_small(tmp_path):
+    """--dump-outputs: float64 .npy files within 64 MB; a field larger than DUMP_DOFS is written as the same seeded sample
+    (sorted, distinct, in range) on every call, a smaller one whole"""
+    import numpy as np
+    import torch
+
+    n = 3 * bench.DUMP_DOFS + 12345
+    x = torch.arange(n, dtype=torch.float64) * 0.5
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), x, (1.25, 7.5))
+    files = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert files == ["mass_max.npy", "u.npy", "u_index.npy"]
+    total = 0
+    for f in files:
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype == np.float64 and np.array_equal(a, b), f
+        total += (tmp_path / "a" / f).stat().st_size
+    assert total <= 64 << 20
+    idx, u = np.load(tmp_path / "a" / "u_index.npy"), np.load(tmp_path / "a" / "u.npy")
+    assert idx.size == u.size == bench.DUMP_DOFS
+    assert idx[0] >= 0 and idx[-1] < n and np.all(np.diff(idx) > 0)
+    assert np.array_equal(u, idx * 0.5)
+    assert np.array_equal(np.load(tmp_path / "a" / "mass_max.npy"), [1.25, 7.5])
+    bench.dump_outputs(str(tmp_path / "c"), x[:1000], (0.0, 0.0))
+    assert np.array_equal(np.load(tmp_path / "c" / "u.npy"), x[:1000].numpy())
+    assert np.array_equal(np.load(tmp_path / "c" / "u_index.npy"), np.arange(1000))

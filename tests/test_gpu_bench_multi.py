@@ -30,7 +30,7 @@ def run_bench(n, extra_env=None, args=("--rs", "2", "--steps", "2", "--warmup", 
 @pytest.mark.parametrize("n,partition", [(2, "2x1x1"), (8, "2x2x2")])
 def test_bench_gpus_n_on_one_gpu(n, partition):
     os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
-    p = run_bench(n)
+    p = run_bench(n, args=("--rs", "2", "--steps", "2", "--warmup", "1", "--full"))
     assert p.returncode == 0, (p.returncode, p.stdout[-1500:], p.stderr[-3000:])
     line = json.loads(p.stdout.strip().splitlines()[-1])
     assert len(p.stdout.strip().splitlines()[-1]) < 6144
@@ -74,3 +74,33 @@ def test_bench_gpus_1_prints_the_cpp_loop_too():
     assert p.returncode == 0, (p.stdout[-1500:], p.stderr[-3000:])
     line = json.loads(p.stdout.strip().splitlines()[-1])
     assert line["n_gpus"] == 1 and line["cpp_loop"]["pass"] is True and line["cpp_loop"]["value"] > 0
+
+
+def test_bench_plain_run_is_the_headline_and_dumps_its_outputs(tmp_path):
+    """a plain `--gpus 1` run times exactly --steps steps and carries the headline only (the other blocks need --full);
+    `--dump-outputs DIR` writes the field of the last timed step, the same for the same arguments"""
+    import numpy as np
+
+    env = dict(os.environ)
+    for k in ("WORLD_SIZE", "RANK", "RMH_BENCH_ONE_GPU"):
+        env.pop(k, None)
+    dumps = []
+    for run in ("a", "b"):
+        d = tmp_path / run
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--rs", "2", "--steps", "3", "--warmup", "1",
+                            "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
+        assert p.returncode == 0, (p.stdout[-1500:], p.stderr[-3000:])
+        line = json.loads(p.stdout.strip().splitlines()[-1])
+        assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["value"] > 0
+        assert line["unit"] == "MDOFs*RK-stage/s" and line["higher_is_better"] is True and line["dtype"] == "f64"
+        # value = dofs x 3 stages x steps / wall time of the steps = 3e-3 x dofs / ms_per_step
+        dofs = line["config"]["global_dofs"]
+        assert dofs == 12**3 * 64
+        assert abs(line["value"] - 3e-3 * dofs / line["ms_per_step"]) <= 1e-4 * line["value"]
+        for k in ("p6", "mass_check", "cpu_baseline", "transport", "sustained", "lo4", "granular", "cpp_loop", "configs0_2d"):
+            assert k not in line, k
+        u, idx, mm = (np.load(d / f) for f in ("u.npy", "u_index.npy", "mass_max.npy"))
+        assert u.dtype == idx.dtype == mm.dtype == np.float64 and u.size == idx.size == dofs
+        assert abs(mm[0] - line["config"]["final_mass"]) <= 1e-12 * abs(mm[0]) and mm[1] == u.max()
+        dumps.append(u)
+    assert np.allclose(dumps[0], dumps[1], rtol=0.0, atol=1e-12 * np.abs(dumps[0]).max())
