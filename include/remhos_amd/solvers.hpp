@@ -248,6 +248,20 @@ public:
                        const Array<bool> &active_dofs, Vector &d_us) override;
 };
 
+// remhos_fct.hpp:157-174 (-fct 4): Zalesak-type limiting of the element's antidiffusive fluxes with the consistent mass matrix
+// of the mesh at the operator's time (rmh_fct_projection; the vector m is not read, like in the reference)
+class ElementFCTProjection : public FCTSolver
+{
+public:
+   ElementFCTProjection(ParFiniteElementSpace &space, real_t dt) : FCTSolver(space, NULL, dt, false) {}
+   void CalcFCTSolution(const ParGridFunction &u, const Vector &m, const Vector &du_ho, const Vector &du_lo,
+                        const Vector &u_min, const Vector &u_max, Vector &du) const override;
+   // (product remap with this solver, remhos_fct.cpp:733-758, is not built: aborts)
+   void CalcFCTProduct(const ParGridFunction &us, const Vector &m, const Vector &d_us_HO, const Vector &d_us_LO,
+                       Vector &s_min, Vector &s_max, const Vector &u_new, const Array<bool> &active_el,
+                       const Array<bool> &active_dofs, Vector &d_us) override;
+};
+
 // Local bounds (remhos_tools.hpp:114-189): element extrema and overlap bounds
 class DofInfo
 {

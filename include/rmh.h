@@ -78,7 +78,7 @@ typedef struct {
  * BASELINE configs[0]'s mesh family.  Layout: x0 / vel [ne][2][9] (node a = ax + 3*ay), face_nbr [ne][4] (f = 2*c + side),
  * `stencil27` = the 3 x 3 element stencil [ne][9] (entry (ox+1) + 3*(oy+1)), ne_ghost = 0, subcell_vel [ne][2][(p+1)^2] or NULL; E-vectors
  * carry (p+1)^2 doubles per element; Q = p + 2 quadrature points per direction.  Entry points: rmh_setup,
- * rmh_ho_apply, rmh_lumped_mass, rmh_compute_lumped_mass, rmh_lo_massavg, rmh_lo_rd, rmh_lo_rdsubcell, rmh_elem_minmax, rmh_bounds, rmh_fct_clipscale,
+ * rmh_ho_apply, rmh_lumped_mass, rmh_compute_lumped_mass, rmh_lo_massavg, rmh_lo_rd, rmh_lo_rdsubcell, rmh_elem_minmax, rmh_bounds, rmh_fct_clipscale, rmh_fct_projection,
  * rmh_limit_fused, rmh_limit_fused_lo, rmh_stage_fused (the whole rank: HO kernel, RD solver for lo 3 / 4 and the fused limiter run
  * as a sequence inside the library; no tokens), the mass-rule / bounds-type / dt-control setters and getters, timers.  Everything
  * else (element ranges of a stage, product fields, exchange) returns RMH_ERR_INVALID for a 2-D context. */
@@ -261,6 +261,15 @@ int rmh_bounds(rmh_ctx *ctx, const double *xe_min, const double *xe_max,
 int rmh_fct_clipscale(rmh_ctx *ctx, const double *u, const double *m,
                       const double *du_ho, const double *du_lo,
                       const double *u_min, const double *u_max, double dt, double *du);
+
+/* FCTSolver::CalcFCTSolution, ElementFCTProjection (-fct 4; remhos_fct.hpp:157-174, remhos_fct.cpp:613-731): limits the
+ * antidiffusive fluxes between every pair of dofs of an element.  Like the reference's, the solver builds the element's
+ * consistent mass matrix itself -- from the mesh at the pseudo-time of the last rmh_setup -- and takes its row sums as the
+ * lumped mass: `m` is the argument of the FCTSolver interface and is not read (the reference ignores it too); it must not be
+ * NULL.  dt > 0.  The result is the same bits from run to run (no atomics).  dim = 3 and dim = 2, every order. */
+int rmh_fct_projection(rmh_ctx *ctx, const double *u, const double *m,
+                       const double *du_ho, const double *du_lo,
+                       const double *u_min, const double *u_max, double dt, double *du);
 
 /* ---- Product-field remap (-ps; second block of AdvectionOperator::LimitMult, remhos.cpp:1848-1915) ----------------
  * Flags are device byte arrays (mfem::Array<bool>): active_el[ne], active_dofs[ne * ndof].

@@ -56,6 +56,8 @@ typedef struct {
                          monotonicity check of the global extrema at the top of every step (remhos.cpp:1218-1262).  A violation
                          prints the reference's message and aborts.  rmhd_run / rmhd_run_rank; costs the granular bounds + LO
                          kernels beside a fused stage.                                                                       */
+   int fct_type;      /* -fct: 2 clip + scale (0 means 2), 4 element FCT projection (remhos_fct.cpp:613-731: the granular solver
+                         sequence only -- fused = 0, no -ps, rmhd_run / rmhd_run_state / rmhd_run_rank)                          */
 } rmhd_config;
 
 typedef struct {

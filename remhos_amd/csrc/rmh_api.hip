@@ -5,6 +5,7 @@
 #include "rmh_ho2.hpp"
 #include "rmh_stream.hpp"
 #include "rmh_2d.hpp"
+#include "rmh_efp.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -899,6 +900,36 @@ int rmh_fct_clipscale(rmh_ctx *c, const double *u, const double *m, const double
    {
       RMH_DISPATCH(c, hipLaunchKernelGGL((fct_clipscale_kernel<P>), dim3(c->ne), dim3(KCfg<P>::NT), 0, c->stream, u, m,
                                          du_ho, du_lo, u_min, u_max, dt, du));
+   }
+   RMH_HIP(hipGetLastError());
+   return timer_end(c, 3, ep);
+}
+
+int rmh_fct_projection(rmh_ctx *c, const double *u, const double *m, const double *du_ho, const double *du_lo,
+                       const double *u_min, const double *u_max, double dt, double *du)
+{
+   if (!c || !u || !m || !du_ho || !du_lo || !u_min || !u_max || !du)
+   {
+      return fail(RMH_ERR_INVALID, "null argument");
+   }
+   if (!(dt > 0.0)) { return fail(RMH_ERR_INVALID, "dt must be positive"); }
+   RMH_ENTER(c);
+   extrema_dropped(c);
+   EventPair ep;
+   int rc = timer_begin(c, 3, ep);
+   if (rc) { return rc; }
+   const int move = c->exec_mode == 1 ? 1 : 0;
+   if (c->dim == 2)
+   {
+      RMH_DISPATCH(c, hipLaunchKernelGGL((fct_projection_kernel<P, 2>), dim3(c->ne), dim3(EfpCfg<P, 2>::NT), 0, c->stream,
+                                         (const double *)c->d_x0, (const double *)c->d_vel, (const double *)c->d_tab, c->t, move, 0,
+                                         u, du_ho, du_lo, u_min, u_max, dt, du));
+   }
+   else
+   {
+      RMH_DISPATCH(c, hipLaunchKernelGGL((fct_projection_kernel<P, 3>), dim3(c->ne), dim3(EfpCfg<P, 3>::NT), 0, c->stream,
+                                         (const double *)c->d_x0h, (const double *)c->d_velh, (const double *)c->d_tab, c->t, move,
+                                         (int)RMH_HIER, u, du_ho, du_lo, u_min, u_max, dt, du));
    }
    RMH_HIP(hipGetLastError());
    return timer_end(c, 3, ep);

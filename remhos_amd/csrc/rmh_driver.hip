@@ -215,6 +215,32 @@ void ClipScaleSolver::CalcFCTProduct(const ParGridFunction &us, const Vector &m,
    }
 }
 
+void ElementFCTProjection::CalcFCTSolution(const ParGridFunction &u, const Vector &m, const Vector &du_ho,
+                                           const Vector &du_lo, const Vector &u_min, const Vector &u_max,
+                                           Vector &du) const
+{
+   RMH_CALL(rmh_fct_projection(pfes.Ctx(), u.Read(), m.Read(), du_ho.Read(), du_lo.Read(), u_min.Read(), u_max.Read(),
+                               dt, du.Write()));
+}
+
+void ElementFCTProjection::CalcFCTProduct(const ParGridFunction &, const Vector &, const Vector &, const Vector &, Vector &,
+                                          Vector &, const Vector &, const Array<bool> &, const Array<bool> &, Vector &)
+{
+   RMH_VERIFY(false, "Product remap (-ps) is not implemented for ElementFCTProjection (-fct 4)");
+}
+
+// -fct of rmhd_config: what the entry points below accept (0 on success, else the message is in g_driver_error)
+static int check_fct_type(const rmhd_config *cfg, bool partitioned)
+{
+   const int fct = cfg->fct_type;
+   if (fct != 0 && fct != 2 && fct != 4) { g_driver_error = "fct_type must be 2 (clip + scale; 0 means 2) or 4 (element FCT projection)"; return -1; }
+   if (fct != 4) { return 0; }
+   if (partitioned) { g_driver_error = "rmhd_run_partitioned runs the one-kernel stage, which has clip + scale built in: fct_type 4 runs through rmhd_run / rmhd_run_rank with fused = 0"; return -1; }
+   if (cfg->fused) { g_driver_error = "fct_type 4: the fused limiter and the one-kernel stage have clip + scale built in (fused must be 0)"; return -1; }
+   if (cfg->ps) { g_driver_error = "fct_type 4: product remap (ps) is not implemented for the element FCT projection"; return -1; }
+   return 0;
+}
+
 // remhos.cpp:1557-1594
 static void report_violation(const rmh_violation &v, const std::string &info)
 {
@@ -550,6 +576,7 @@ extern "C" int rmhd_run_rank(const rmhd_config *cfg, const char *comm_id_file, i
 {
    if (!cfg || !res) { g_driver_error = "null argument"; return -1; }
    std::memset(res, 0, sizeof(*res));
+   if (check_fct_type(cfg, false) != 0) { return -1; }
    CaseConfig cc = to_config(*cfg);
    const int nranks = cc.px * cc.py * cc.pz;
    const bool rccl_ranks = comm_id_file && comm_id_file[0];
@@ -662,7 +689,9 @@ extern "C" int rmhd_run_rank(const rmhd_config *cfg, const char *comm_id_file, i
       else if (cc.lo_type == 3) { lo_solver = new PAResidualDistribution(pfes); }
       else { lo_solver = new PAResidualDistributionSubcell(pfes); }
       double dt = cd.dt;
-      FCTSolver *fct_solver = new ClipScaleSolver(pfes, nullptr, dt);
+      FCTSolver *fct_solver = nullptr; // remhos.cpp:983-995
+      if (cfg->fct_type == 4) { fct_solver = new ElementFCTProjection(pfes, dt); }
+      else { fct_solver = new ClipScaleSolver(pfes, nullptr, dt); }
       // -ps / -s 11|12|13 (remhos.cpp:484-507, 875-904): block vector [u | us], IDP solvers.  They limit a COMBINATION of
       // the stage's HO rate and the earlier limited updates, so the stage cannot be the one-kernel rmh_stage_fused:
       // HO kernel + fused limiter kernel (fused = 1) or the reference's call sequence (fused = 0).
@@ -1068,6 +1097,7 @@ extern "C" int rmhd_run_partitioned(const rmhd_config *cfg, const char *comm_id_
    CaseConfig cc0 = to_config(*cfg);
    const int nranks = cc0.px * cc0.py * cc0.pz;
    const bool rccl = comm_id_file && comm_id_file[0];
+   if (check_fct_type(cfg, true) != 0) { return -1; }
    if (!cfg->fused) { g_driver_error = "rmhd_run_partitioned runs the one-kernel stage (fused = 1)"; return -1; }
    std::vector<Block> blocks(rccl ? 1 : nranks);
    auto cleanup = [&]()
