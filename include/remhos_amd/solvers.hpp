@@ -198,6 +198,21 @@ public:
    void CalcLOSolution(const Vector &u, Vector &du) const override;
 };
 
+// remhos_lo.hpp:48-66 (-lo 1): discrete upwinding of the volume-only convection form k (remhos.cpp:646-657, 931-935) plus the
+// lumped upwind face fluxes.  k is block diagonal, so the assembled matrix, its symmetry map, the lumped mass vector and the
+// Assembly object of the reference's constructor have no counterpart: the kernel forms the element's dense rows and columns on
+// the mesh of the operator's time and reads the context's lumped mass (rmh_lo_upwind).  updateD: remap mode (K changes with
+// the mesh); the kernel re-forms D on every call either way.
+class DiscreteUpwind : public LOSolver
+{
+protected:
+   const bool update_D;
+
+public:
+   DiscreteUpwind(ParFiniteElementSpace &space, bool updateD) : LOSolver(space), update_D(updateD) {}
+   void CalcLOSolution(const Vector &u, Vector &du) const override;
+};
+
 // Monotone, High-order, Conservative Solver (remhos_fct.hpp:31-90)
 class FCTSolver
 {
@@ -257,6 +272,28 @@ public:
    void CalcFCTSolution(const ParGridFunction &u, const Vector &m, const Vector &du_ho, const Vector &du_lo,
                         const Vector &u_min, const Vector &u_max, Vector &du) const override;
    // (product remap with this solver, remhos_fct.cpp:733-758, is not built: aborts)
+   void CalcFCTProduct(const ParGridFunction &us, const Vector &m, const Vector &d_us_HO, const Vector &d_us_LO,
+                       Vector &s_min, Vector &s_max, const Vector &u_new, const Array<bool> &active_el,
+                       const Array<bool> &active_dofs, Vector &d_us) override;
+};
+
+// remhos_fct.hpp:92-135 (-fct 1): Zalesak limiting of the fluxes f_ij = dt d_ij (u_i - u_j) + dt M_ij (duH_i - duH_j) of K_HO and
+// the consistent mass of the mesh at the operator's time.  On tensor lattices every entry of K_HO between two elements is >= 0,
+// so its d_ij and flux vanish and the solver is element-local (rmh_fct_fluxbased): the assembled
+// matrices and the symmetry map of the reference's constructor have no counterpart.  m is the lumped mass (it IS read here).
+class FluxBasedFCT : public FCTSolver
+{
+protected:
+   const int iter_cnt;
+
+public:
+   FluxBasedFCT(ParFiniteElementSpace &space, SmoothnessIndicator *si, real_t delta_t, int fct_iterations = 1)
+      : FCTSolver(space, si, delta_t, true), iter_cnt(fct_iterations)
+   {
+   }
+   void CalcFCTSolution(const ParGridFunction &u, const Vector &m, const Vector &du_ho, const Vector &du_lo,
+                        const Vector &u_min, const Vector &u_max, Vector &du) const override;
+   // (product remap with this solver, remhos_fct.cpp:183-293, is not built: aborts)
    void CalcFCTProduct(const ParGridFunction &us, const Vector &m, const Vector &d_us_HO, const Vector &d_us_LO,
                        Vector &s_min, Vector &s_max, const Vector &u_new, const Array<bool> &active_el,
                        const Array<bool> &active_dofs, Vector &d_us) override;

@@ -78,7 +78,7 @@ typedef struct {
  * BASELINE configs[0]'s mesh family.  Layout: x0 / vel [ne][2][9] (node a = ax + 3*ay), face_nbr [ne][4] (f = 2*c + side),
  * `stencil27` = the 3 x 3 element stencil [ne][9] (entry (ox+1) + 3*(oy+1)), ne_ghost = 0, subcell_vel [ne][2][(p+1)^2] or NULL; E-vectors
  * carry (p+1)^2 doubles per element; Q = p + 2 quadrature points per direction.  Entry points: rmh_setup,
- * rmh_ho_apply, rmh_lumped_mass, rmh_compute_lumped_mass, rmh_lo_massavg, rmh_lo_rd, rmh_lo_rdsubcell, rmh_elem_minmax, rmh_bounds, rmh_fct_clipscale, rmh_fct_projection,
+ * rmh_ho_apply, rmh_lumped_mass, rmh_compute_lumped_mass, rmh_lo_massavg, rmh_lo_rd, rmh_lo_rdsubcell, rmh_lo_upwind, rmh_elem_minmax, rmh_bounds, rmh_fct_clipscale, rmh_fct_projection, rmh_fct_fluxbased,
  * rmh_limit_fused, rmh_limit_fused_lo, rmh_stage_fused (the whole rank: HO kernel, RD solver for lo 3 / 4 and the fused limiter run
  * as a sequence inside the library; no tokens), the mass-rule / bounds-type / dt-control setters and getters, timers.  Everything
  * else (element ranges of a stage, product fields, exchange) returns RMH_ERR_INVALID for a 2-D context. */
@@ -270,6 +270,26 @@ int rmh_fct_clipscale(rmh_ctx *ctx, const double *u, const double *m,
 int rmh_fct_projection(rmh_ctx *ctx, const double *u, const double *m,
                        const double *du_ho, const double *du_lo,
                        const double *u_min, const double *u_max, double dt, double *du);
+
+/* LOSolver::CalcLOSolution, DiscreteUpwind (-lo 1; remhos_lo.hpp:48-66, remhos_lo.cpp:31-100): discrete upwinding of the
+ * volume-only convection form (remhos.cpp:646-657, 931-935; block diagonal: the kernel forms the element's dense rows and
+ * columns, no assembled matrix) plus the lumped upwind face fluxes (remhos_tools.cpp:876-913 with alpha = 0) -- on the mesh
+ * at the pseudo-time of the last rmh_setup.  Reads the face layers of the face neighbours like rmh_lo_rd (ghost values must
+ * be set and no exchange of u in flight).  Divides by the context's lumped mass: the one rmh_ho_apply left since the last
+ * rmh_setup, otherwise it is formed first.  The same bits from run to run.  dim = 3 and dim = 2, every order. */
+int rmh_lo_upwind(rmh_ctx *ctx, const double *u, double *du_lo);
+
+/* FCTSolver::CalcFCTSolution, FluxBasedFCT (-fct 1; remhos_fct.hpp:92-135, remhos_fct.cpp:155-181, 295-446; one FCT
+ * iteration, remhos.cpp:1093): limits the fluxes dt d_ij (u_i - u_j) + dt M_ij (duH_i - duH_j) between every pair of dofs
+ * of an element, with d_ij from K_HO (volume form minus the own-face blocks of the upwind trace form) and the element's
+ * consistent mass matrix, both built by the solver on the mesh at the pseudo-time of the last rmh_setup.  The entries of
+ * K_HO between two elements are >= 0 on these meshes, so their fluxes are exactly zero and no neighbour is read
+ * (DESIGN.md section 3.14).  `m` is the lumped mass and IS read (remhos_fct.cpp:391-393, 440).  dt > 0.  Contexts with
+ * ghost elements (ne_ghost > 0) return RMH_ERR_INVALID.  The same bits from run to run (no atomics).  dim = 3 and
+ * dim = 2, every order. */
+int rmh_fct_fluxbased(rmh_ctx *ctx, const double *u, const double *m,
+                      const double *du_ho, const double *du_lo,
+                      const double *u_min, const double *u_max, double dt, double *du);
 
 /* ---- Product-field remap (-ps; second block of AdvectionOperator::LimitMult, remhos.cpp:1848-1915) ----------------
  * Flags are device byte arrays (mfem::Array<bool>): active_el[ne], active_dofs[ne * ndof].

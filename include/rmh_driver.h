@@ -24,7 +24,7 @@ typedef struct {
    double dt;         /* -dt (< 0: CFL rule remhos.cpp:538-553)                               */
    double t_final;    /* -tf                                                                  */
    int max_steps;     /* -ms (< 0: none)                                                      */
-   int lo_type;       /* -lo : 3 RD, 4 subcell RD, 5 mass-based average                       */
+   int lo_type;       /* -lo : 1 discrete upwind (fused = 0), 3 RD, 4 subcell RD, 5 mass-based average */
    int fused;         /* 1: LimitMult through rmh_limit_fused, 0: the reference's call sequence */
    int px, py, pz;    /* box partition of the element lattice                                 */
    int rank;          /* which block this process owns                                        */
@@ -57,7 +57,9 @@ typedef struct {
                          prints the reference's message and aborts.  rmhd_run / rmhd_run_rank; costs the granular bounds + LO
                          kernels beside a fused stage.                                                                       */
    int fct_type;      /* -fct: 2 clip + scale (0 means 2), 4 element FCT projection (remhos_fct.cpp:613-731: the granular solver
-                         sequence only -- fused = 0, no -ps, rmhd_run / rmhd_run_state / rmhd_run_rank)                          */
+                         sequence only -- fused = 0, no -ps, rmhd_run / rmhd_run_state / rmhd_run_rank), 1 flux-based FCT
+                         (remhos_fct.cpp:155-181, 295-446: like 4, and one block, no pa -- remhos.cpp:1088).  lo_type 1
+                         (DiscreteUpwind, remhos_lo.cpp:31-100) has the same conditions as fct_type 1, except pa.            */
 } rmhd_config;
 
 typedef struct {

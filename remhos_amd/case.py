@@ -72,7 +72,7 @@ def make_config(mesh="periodic-cube", rs=1, order=3, problem=10, dt=-1.0, t_fina
     c.ps, c.ode_solver = int(ps), int(ode_solver)
     c.tile_rows = int(tile_rows)
     c.verify_bounds = int(verify_bounds)
-    c.fct_type = int(fct_type)  # 0 / 2 clip + scale, 4 element FCT projection (fused = 0)
+    c.fct_type = int(fct_type)  # 0 / 2 clip + scale, 4 element FCT projection, 1 flux-based FCT (fused = 0)
     return c
 
 

@@ -6,6 +6,7 @@
 #include "rmh_stream.hpp"
 #include "rmh_2d.hpp"
 #include "rmh_efp.hpp"
+#include "rmh_upwind.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -930,6 +931,90 @@ int rmh_fct_projection(rmh_ctx *c, const double *u, const double *m, const doubl
       RMH_DISPATCH(c, hipLaunchKernelGGL((fct_projection_kernel<P, 3>), dim3(c->ne), dim3(EfpCfg<P, 3>::NT), 0, c->stream,
                                          (const double *)c->d_x0h, (const double *)c->d_velh, (const double *)c->d_tab, c->t, move,
                                          (int)RMH_HIER, u, du_ho, du_lo, u_min, u_max, dt, du));
+   }
+   RMH_HIP(hipGetLastError());
+   return timer_end(c, 3, ep);
+}
+
+namespace
+{
+UpwArgs upwind_args(const rmh_ctx *c)
+{
+   UpwArgs a;
+   a.x0 = c->dim == 2 ? c->d_x0 : c->d_x0h;
+   a.vel = c->dim == 2 ? c->d_vel : c->d_velh;
+   a.tab = c->d_tab;
+   a.t = c->t;
+   a.move = c->exec_mode == 1 ? 1 : 0;
+   a.hier = c->dim == 2 ? 0 : (int)RMH_HIER;
+   a.alpha = c->exec_mode == 1 ? 1.0 : -1.0; // remhos.cpp:648-657
+   a.face_nbr = c->d_nbr;
+   a.ne_owned = c->ne;
+   a.u_ghost = c->u_ghost;
+   a.gh_ustride = c->gh_ustride;
+   a.gh_compact = c->gh_compact;
+   return a;
+}
+} // namespace
+
+int rmh_lo_upwind(rmh_ctx *c, const double *u, double *du_lo)
+{
+   if (!c || !u || !du_lo) { return fail(RMH_ERR_INVALID, "null argument"); }
+   if (c->ng > 0 && !c->u_ghost) { return fail(RMH_ERR_STATE, "ghost values of u not set"); }
+   if (const char *why = ghosts_in_flight(c)) { return fail(RMH_ERR_STATE, why); }
+   RMH_ENTER(c);
+   extrema_dropped(c);
+   // the lumped mass of this geometry: rmh_ho_apply has just left it in the context, otherwise it is formed here
+   if (!c->ho_done)
+   {
+      const int rc = rmh_compute_lumped_mass(c, c->t, c->d_m);
+      if (rc) { return rc; }
+   }
+   EventPair ep;
+   int rc = timer_begin(c, 2, ep);
+   if (rc) { return rc; }
+   const UpwArgs a = upwind_args(c);
+   if (c->dim == 2)
+   {
+      RMH_DISPATCH(c, hipLaunchKernelGGL((lo_upwind_kernel<P, 2>), dim3(c->ne), dim3(EfpCfg<P, 2>::NT), 0, c->stream, a, u,
+                                         (const double *)c->d_m, du_lo));
+   }
+   else
+   {
+      RMH_DISPATCH(c, hipLaunchKernelGGL((lo_upwind_kernel<P, 3>), dim3(c->ne), dim3(EfpCfg<P, 3>::NT), 0, c->stream, a, u,
+                                         (const double *)c->d_m, du_lo));
+   }
+   RMH_HIP(hipGetLastError());
+   return timer_end(c, 2, ep);
+}
+
+int rmh_fct_fluxbased(rmh_ctx *c, const double *u, const double *m, const double *du_ho, const double *du_lo,
+                      const double *u_min, const double *u_max, double dt, double *du)
+{
+   if (!c || !u || !m || !du_ho || !du_lo || !u_min || !u_max || !du)
+   {
+      return fail(RMH_ERR_INVALID, "null argument");
+   }
+   if (!(dt > 0.0)) { return fail(RMH_ERR_INVALID, "dt must be positive"); }
+   if (c->ng > 0)
+   {
+      return fail(RMH_ERR_INVALID, "rmh_fct_fluxbased: contexts with ghost elements are not supported (the solver runs on one rank)");
+   }
+   RMH_ENTER(c);
+   extrema_dropped(c);
+   EventPair ep;
+   int rc = timer_begin(c, 3, ep);
+   if (rc) { return rc; }
+   const UpwArgs a = upwind_args(c);
+   if (c->dim == 2)
+   {
+      RMH_DISPATCH(c, hipLaunchKernelGGL((fct_fluxbased_kernel<P, 2>), dim3(c->ne), dim3(EfpCfg<P, 2>::NT), 0, c->stream, a, u, m,
+                                         du_ho, du_lo, u_min, u_max, dt, du));
+   }
+   else
+   {
+      RMH_DISPATCH(c, hipLaunchKernelGGL((fct_fluxbased_kernel<P, 3>), dim3(c->ne), dim3(EfpCfg<P, 3>::NT), 0, c->stream, a, u, m,
+                                         du_ho, du_lo, u_min, u_max, dt, du));
    }
    RMH_HIP(hipGetLastError());
    return timer_end(c, 3, ep);

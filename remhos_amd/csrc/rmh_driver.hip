@@ -229,11 +229,42 @@ void ElementFCTProjection::CalcFCTProduct(const ParGridFunction &, const Vector 
    RMH_VERIFY(false, "Product remap (-ps) is not implemented for ElementFCTProjection (-fct 4)");
 }
 
+void DiscreteUpwind::CalcLOSolution(const Vector &u, Vector &du) const
+{
+   // remhos_lo.cpp:43-100 (D is rebuilt on the mesh of the operator's time by the kernel: update_D)
+   RMH_CALL(rmh_lo_upwind(pfes.Ctx(), u.Read(), du.Write()));
+}
+
+void FluxBasedFCT::CalcFCTSolution(const ParGridFunction &u, const Vector &m, const Vector &du_ho, const Vector &du_lo,
+                                   const Vector &u_min, const Vector &u_max, Vector &du) const
+{
+   RMH_VERIFY(smth_indicator == NULL, "TODO: update SI bounds."); // remhos_fct.cpp:160
+   RMH_VERIFY(iter_cnt == 1, "FluxBasedFCT: one FCT iteration (remhos.cpp:1093)");
+   RMH_CALL(rmh_fct_fluxbased(pfes.Ctx(), u.Read(), m.Read(), du_ho.Read(), du_lo.Read(), u_min.Read(), u_max.Read(), dt,
+                              du.Write()));
+}
+
+void FluxBasedFCT::CalcFCTProduct(const ParGridFunction &, const Vector &, const Vector &, const Vector &, Vector &, Vector &,
+                                  const Vector &, const Array<bool> &, const Array<bool> &, Vector &)
+{
+   RMH_VERIFY(false, "Product remap (-ps) is not implemented for FluxBasedFCT (-fct 1)");
+}
+
 // -fct of rmhd_config: what the entry points below accept (0 on success, else the message is in g_driver_error)
 static int check_fct_type(const rmhd_config *cfg, bool partitioned)
 {
    const int fct = cfg->fct_type;
-   if (fct != 0 && fct != 2 && fct != 4) { g_driver_error = "fct_type must be 2 (clip + scale; 0 means 2) or 4 (element FCT projection)"; return -1; }
+   if (fct != 0 && fct != 1 && fct != 2 && fct != 4) { g_driver_error = "fct_type must be 1 (flux-based FCT), 2 (clip + scale; 0 means 2) or 4 (element FCT projection)"; return -1; }
+   if (fct == 1 || cfg->lo_type == 1)
+   {
+      // DiscreteUpwind (-lo 1) and FluxBasedFCT (-fct 1) run through the granular solver sequence on one block
+      const char *who = fct == 1 ? "fct_type 1" : "lo_type 1";
+      if (partitioned || cfg->px * cfg->py * cfg->pz > 1) { g_driver_error = std::string(who) + ": partitioned runs are not built for the DiscreteUpwind / FluxBasedFCT solvers (one block, rmhd_run with fused = 0)"; return -1; }
+      if (cfg->fused) { g_driver_error = std::string(who) + ": the fused limiter and the one-kernel stage have their LO solver and clip + scale built in (fused must be 0)"; return -1; }
+      if (cfg->ps) { g_driver_error = std::string(who) + ": product remap (ps) is not implemented for the DiscreteUpwind / FluxBasedFCT solvers"; return -1; }
+      if (fct == 1 && cfg->pa) { g_driver_error = "Flux-based FCT and PA are incompatible."; return -1; } // remhos.cpp:1088
+      if (fct == 1 && cfg->self_wrap) { g_driver_error = "fct_type 1: a self-wrapped block has ghost elements, which rmh_fct_fluxbased does not take"; return -1; }
+   }
    if (fct != 4) { return 0; }
    if (partitioned) { g_driver_error = "rmhd_run_partitioned runs the one-kernel stage, which has clip + scale built in: fct_type 4 runs through rmhd_run / rmhd_run_rank with fused = 0"; return -1; }
    if (cfg->fused) { g_driver_error = "fct_type 4: the fused limiter and the one-kernel stage have clip + scale built in (fused must be 0)"; return -1; }
@@ -686,11 +717,13 @@ extern "C" int rmhd_run_rank(const rmhd_config *cfg, const char *comm_id_file, i
       else { ho_solver = new LocalInverseHOSolver(pfes, cfg->pa != 0); }
       LOSolver *lo_solver = nullptr;
       if (cc.lo_type == 5) { lo_solver = new MassBasedAvg(pfes, *ho_solver, nullptr); }
+      else if (cc.lo_type == 1) { lo_solver = new DiscreteUpwind(pfes, cd.exec_mode == 1); } // remhos.cpp:931-936
       else if (cc.lo_type == 3) { lo_solver = new PAResidualDistribution(pfes); }
       else { lo_solver = new PAResidualDistributionSubcell(pfes); }
       double dt = cd.dt;
       FCTSolver *fct_solver = nullptr; // remhos.cpp:983-995
       if (cfg->fct_type == 4) { fct_solver = new ElementFCTProjection(pfes, dt); }
+      else if (cfg->fct_type == 1) { fct_solver = new FluxBasedFCT(pfes, nullptr, dt, 1); } // remhos.cpp:1086-1096
       else { fct_solver = new ClipScaleSolver(pfes, nullptr, dt); }
       // -ps / -s 11|12|13 (remhos.cpp:484-507, 875-904): block vector [u | us], IDP solvers.  They limit a COMBINATION of
       // the stage's HO rate and the earlier limited updates, so the stage cannot be the one-kernel rmh_stage_fused:
