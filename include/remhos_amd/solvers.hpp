@@ -203,13 +203,19 @@ public:
 // Assembly object of the reference's constructor have no counterpart: the kernel forms the element's dense rows and columns on
 // the mesh of the operator's time and reads the context's lumped mass (rmh_lo_upwind).  updateD: remap mode (K changes with
 // the mesh); the kernel re-forms D on every call either way.
+// precond (-lo 2, remhos.cpp:749-771, 937-942): the reference hands the same class the matrix of PrecondConvectionIntegrator,
+// K_e = M_L,e M_e^-1 C_e (remhos_tools.cpp:975-1031), in the place of k; here the flag selects rmh_lo_upwind_prec.
 class DiscreteUpwind : public LOSolver
 {
 protected:
    const bool update_D;
+   const bool preconditioned;
 
 public:
-   DiscreteUpwind(ParFiniteElementSpace &space, bool updateD) : LOSolver(space), update_D(updateD) {}
+   DiscreteUpwind(ParFiniteElementSpace &space, bool updateD, bool precond = false)
+      : LOSolver(space), update_D(updateD), preconditioned(precond)
+   {
+   }
    void CalcLOSolution(const Vector &u, Vector &du) const override;
 };
 

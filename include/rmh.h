@@ -78,7 +78,7 @@ typedef struct {
  * BASELINE configs[0]'s mesh family.  Layout: x0 / vel [ne][2][9] (node a = ax + 3*ay), face_nbr [ne][4] (f = 2*c + side),
  * `stencil27` = the 3 x 3 element stencil [ne][9] (entry (ox+1) + 3*(oy+1)), ne_ghost = 0, subcell_vel [ne][2][(p+1)^2] or NULL; E-vectors
  * carry (p+1)^2 doubles per element; Q = p + 2 quadrature points per direction.  Entry points: rmh_setup,
- * rmh_ho_apply, rmh_lumped_mass, rmh_compute_lumped_mass, rmh_lo_massavg, rmh_lo_rd, rmh_lo_rdsubcell, rmh_lo_upwind, rmh_elem_minmax, rmh_bounds, rmh_fct_clipscale, rmh_fct_projection, rmh_fct_fluxbased,
+ * rmh_ho_apply, rmh_lumped_mass, rmh_compute_lumped_mass, rmh_lo_massavg, rmh_lo_rd, rmh_lo_rdsubcell, rmh_lo_upwind, rmh_lo_upwind_prec, rmh_elem_minmax, rmh_bounds, rmh_fct_clipscale, rmh_fct_projection, rmh_fct_fluxbased,
  * rmh_limit_fused, rmh_limit_fused_lo, rmh_stage_fused (the whole rank: HO kernel, RD solver for lo 3 / 4 and the fused limiter run
  * as a sequence inside the library; no tokens), the mass-rule / bounds-type / dt-control setters and getters, timers.  Everything
  * else (element ranges of a stage, product fields, exchange) returns RMH_ERR_INVALID for a 2-D context. */
@@ -278,6 +278,15 @@ int rmh_fct_projection(rmh_ctx *ctx, const double *u, const double *m,
  * be set and no exchange of u in flight).  Divides by the context's lumped mass: the one rmh_ho_apply left since the last
  * rmh_setup, otherwise it is formed first.  The same bits from run to run.  dim = 3 and dim = 2, every order. */
 int rmh_lo_upwind(rmh_ctx *ctx, const double *u, double *du_lo);
+
+/* LOSolver::CalcLOSolution, DiscreteUpwind with the preconditioned matrix (-lo 2, "Preconditioned Discrete Upwind";
+ * remhos.cpp:749-771, 937-942): rmh_lo_upwind with K_e = M_L,e M_e^-1 C_e in the place of the volume convection form C_e
+ * (PrecondConvectionIntegrator, remhos_tools.cpp:975-1031; M_e the consistent element mass, M_L,e its row-sum lumping, both
+ * with the integrator's own rule on the mesh at the pseudo-time of the last rmh_setup).  The kernel factors M_e by Cholesky and
+ * solves for the s columns of C_e in LDS.  Ghost values, the context's lumped mass and run-to-run
+ * bit identity: as rmh_lo_upwind.  dim = 2: every order; dim = 3: orders 1 to 3 -- order >= 4 returns RMH_ERR_INVALID with a
+ * message naming -lo 2 and the order (the dense matrices of an element must fit the LDS). */
+int rmh_lo_upwind_prec(rmh_ctx *ctx, const double *u, double *du_lo);
 
 /* FCTSolver::CalcFCTSolution, FluxBasedFCT (-fct 1; remhos_fct.hpp:92-135, remhos_fct.cpp:155-181, 295-446; one FCT
  * iteration, remhos.cpp:1093): limits the fluxes dt d_ij (u_i - u_j) + dt M_ij (duH_i - duH_j) between every pair of dofs

@@ -24,7 +24,7 @@ typedef struct {
    double dt;         /* -dt (< 0: CFL rule remhos.cpp:538-553)                               */
    double t_final;    /* -tf                                                                  */
    int max_steps;     /* -ms (< 0: none)                                                      */
-   int lo_type;       /* -lo : 1 discrete upwind (fused = 0), 3 RD, 4 subcell RD, 5 mass-based average */
+   int lo_type;       /* -lo : 1 discrete upwind, 2 preconditioned discrete upwind (both fused = 0), 3 RD, 4 subcell RD, 5 mass-based average */
    int fused;         /* 1: LimitMult through rmh_limit_fused, 0: the reference's call sequence */
    int px, py, pz;    /* box partition of the element lattice                                 */
    int rank;          /* which block this process owns                                        */
@@ -59,7 +59,8 @@ typedef struct {
    int fct_type;      /* -fct: 2 clip + scale (0 means 2), 4 element FCT projection (remhos_fct.cpp:613-731: the granular solver
                          sequence only -- fused = 0, no -ps, rmhd_run / rmhd_run_state / rmhd_run_rank), 1 flux-based FCT
                          (remhos_fct.cpp:155-181, 295-446: like 4, and one block, no pa -- remhos.cpp:1088).  lo_type 1
-                         (DiscreteUpwind, remhos_lo.cpp:31-100) has the same conditions as fct_type 1, except pa.            */
+                         (DiscreteUpwind, remhos_lo.cpp:31-100) has the same conditions as fct_type 1, except pa; so has
+                         lo_type 2 (the same solver with M_L M^-1 C, remhos.cpp:749-771), dim = 3: order <= 3.               */
 } rmhd_config;
 
 typedef struct {

@@ -16,7 +16,7 @@ SYMBOLS = [
     "rmh_create", "rmh_destroy", "rmh_last_error", "rmh_version", "rmh_set_stream", "rmh_stream_create_reserving", "rmh_stream_destroy", "rmh_batch_order", "rmh_setup",
     "rmh_set_ghost_u", "rmh_set_ghost_minmax", "rmh_halo_pack", "rmh_ho_apply", "rmh_lumped_mass",
     "rmh_compute_lumped_mass", "rmh_lo_massavg", "rmh_lo_rdsubcell", "rmh_lo_rd", "rmh_elem_minmax", "rmh_bounds",
-    "rmh_fct_clipscale", "rmh_fct_projection", "rmh_lo_upwind", "rmh_fct_fluxbased", "rmh_limit_fused", "rmh_limit_fused_lo", "rmh_stage_fused", "rmh_stage_fused_range", "rmh_stage_fused_chain",
+    "rmh_fct_clipscale", "rmh_fct_projection", "rmh_lo_upwind", "rmh_lo_upwind_prec", "rmh_fct_fluxbased", "rmh_limit_fused", "rmh_limit_fused_lo", "rmh_stage_fused", "rmh_stage_fused_range", "rmh_stage_fused_chain",
     "rmh_halo_pack_records", "rmh_set_ghost_records", "rmh_timers", "rmh_reset_timers", "rmh_enable_timers",
     "rmh_last_cg_iters", "rmh_set_mass_tol", "rmh_get_mass_tol", "rmh_set_mass_completion", "rmh_set_lo_type", "rmh_set_bounds_type", "rmh_set_dt_control",
     "rmh_dt_estimate_reset", "rmh_dt_estimate_update", "rmh_dt_estimate_get", "rmh_invalidate_extrema",
@@ -114,6 +114,7 @@ def load_library(path: str | None = None) -> C.CDLL:
     lib.rmh_fct_clipscale.argtypes = [p, p, p, p, p, p, p, d, p]
     lib.rmh_fct_projection.argtypes = [p, p, p, p, p, p, p, d, p]
     lib.rmh_lo_upwind.argtypes = [p, p, p]
+    lib.rmh_lo_upwind_prec.argtypes = [p, p, p]
     lib.rmh_fct_fluxbased.argtypes = [p, p, p, p, p, p, p, d, p]
     lib.rmh_limit_fused.argtypes = [p, p, p, d, p, p, d, d, d, p]
     lib.rmh_limit_fused_lo.argtypes = [p, p, p, p, d, p, p, d, d, d, p]
@@ -281,6 +282,10 @@ class Context:
     def lo_upwind(self, u, du_lo):
         """DiscreteUpwind (-lo 1) at the geometry of the last setup(t)"""
         self._check(self.lib.rmh_lo_upwind(self.h, _ptr(u), _ptr(du_lo)))
+
+    def lo_upwind_prec(self, u, du_lo):
+        """DiscreteUpwind with the preconditioned matrix M_L M^-1 C (-lo 2) at the geometry of the last setup(t)"""
+        self._check(self.lib.rmh_lo_upwind_prec(self.h, _ptr(u), _ptr(du_lo)))
 
     def fct_fluxbased(self, u, m, du_ho, du_lo, u_min, u_max, dt, du):
         """FluxBasedFCT (-fct 1, one iteration) at the geometry of the last setup(t); m is the lumped mass"""

@@ -7,6 +7,7 @@
 #include "rmh_2d.hpp"
 #include "rmh_efp.hpp"
 #include "rmh_upwind.hpp"
+#include "rmh_pdu.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -984,6 +985,59 @@ int rmh_lo_upwind(rmh_ctx *c, const double *u, double *du_lo)
       RMH_DISPATCH(c, hipLaunchKernelGGL((lo_upwind_kernel<P, 3>), dim3(c->ne), dim3(EfpCfg<P, 3>::NT), 0, c->stream, a, u,
                                          (const double *)c->d_m, du_lo));
    }
+   RMH_HIP(hipGetLastError());
+   return timer_end(c, 2, ep);
+}
+
+namespace
+{
+// (static LDS: 67 KB at s = 64, rmh_pdu.hpp -- gfx950 launches static allocations up to its 160 KiB per CU)
+extern "C++" template <int P, int DIM>
+int launch_lo_upwind_prec(rmh_ctx *c, const UpwArgs &a, const double *u, double *du_lo)
+{
+   hipLaunchKernelGGL((lo_upwind_prec_kernel<P, DIM>), dim3(c->ne), dim3(EfpCfg<P, DIM>::NT), 0, c->stream, a, u,
+                      (const double *)c->d_m, du_lo);
+   return RMH_OK;
+}
+} // namespace
+
+int rmh_lo_upwind_prec(rmh_ctx *c, const double *u, double *du_lo)
+{
+   if (!c || !u || !du_lo) { return fail(RMH_ERR_INVALID, "null argument"); }
+   if (c->dim == 3 && c->p >= 4)
+   {
+      return fail(RMH_ERR_INVALID, "rmh_lo_upwind_prec (-lo 2): order " + std::to_string(c->p) +
+                                      " in 3-D is not supported: the element's dense matrices must fit the LDS (orders 1 to 3 in 3-D, 1 to 6 in 2-D)");
+   }
+   if (c->ng > 0 && !c->u_ghost) { return fail(RMH_ERR_STATE, "ghost values of u not set"); }
+   if (const char *why = ghosts_in_flight(c)) { return fail(RMH_ERR_STATE, why); }
+   RMH_ENTER(c);
+   extrema_dropped(c);
+   // the lumped mass of this geometry: rmh_ho_apply has just left it in the context, otherwise it is formed here
+   if (!c->ho_done)
+   {
+      const int rc = rmh_compute_lumped_mass(c, c->t, c->d_m);
+      if (rc) { return rc; }
+   }
+   EventPair ep;
+   int rc = timer_begin(c, 2, ep);
+   if (rc) { return rc; }
+   const UpwArgs a = upwind_args(c);
+   if (c->dim == 2)
+   {
+      RMH_DISPATCH(c, (rc = launch_lo_upwind_prec<P, 2>(c, a, u, du_lo)));
+   }
+   else
+   {
+      switch (c->p)
+      {
+         case 1: rc = launch_lo_upwind_prec<1, 3>(c, a, u, du_lo); break;
+         case 2: rc = launch_lo_upwind_prec<2, 3>(c, a, u, du_lo); break;
+         case 3: rc = launch_lo_upwind_prec<3, 3>(c, a, u, du_lo); break;
+         default: return fail(RMH_ERR_INVALID, "unsupported order");
+      }
+   }
+   if (rc) { return rc; }
    RMH_HIP(hipGetLastError());
    return timer_end(c, 2, ep);
 }

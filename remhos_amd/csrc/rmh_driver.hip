@@ -232,7 +232,8 @@ void ElementFCTProjection::CalcFCTProduct(const ParGridFunction &, const Vector 
 void DiscreteUpwind::CalcLOSolution(const Vector &u, Vector &du) const
 {
    // remhos_lo.cpp:43-100 (D is rebuilt on the mesh of the operator's time by the kernel: update_D)
-   RMH_CALL(rmh_lo_upwind(pfes.Ctx(), u.Read(), du.Write()));
+   if (preconditioned) { RMH_CALL(rmh_lo_upwind_prec(pfes.Ctx(), u.Read(), du.Write())); } // remhos.cpp:937-942
+   else { RMH_CALL(rmh_lo_upwind(pfes.Ctx(), u.Read(), du.Write())); }
 }
 
 void FluxBasedFCT::CalcFCTSolution(const ParGridFunction &u, const Vector &m, const Vector &du_ho, const Vector &du_lo,
@@ -255,10 +256,10 @@ static int check_fct_type(const rmhd_config *cfg, bool partitioned)
 {
    const int fct = cfg->fct_type;
    if (fct != 0 && fct != 1 && fct != 2 && fct != 4) { g_driver_error = "fct_type must be 1 (flux-based FCT), 2 (clip + scale; 0 means 2) or 4 (element FCT projection)"; return -1; }
-   if (fct == 1 || cfg->lo_type == 1)
+   if (fct == 1 || cfg->lo_type == 1 || cfg->lo_type == 2)
    {
-      // DiscreteUpwind (-lo 1) and FluxBasedFCT (-fct 1) run through the granular solver sequence on one block
-      const char *who = fct == 1 ? "fct_type 1" : "lo_type 1";
+      // DiscreteUpwind (-lo 1, preconditioned: -lo 2) and FluxBasedFCT (-fct 1) run through the granular solver sequence on one block
+      const char *who = fct == 1 ? "fct_type 1" : (cfg->lo_type == 2 ? "lo_type 2" : "lo_type 1");
       if (partitioned || cfg->px * cfg->py * cfg->pz > 1) { g_driver_error = std::string(who) + ": partitioned runs are not built for the DiscreteUpwind / FluxBasedFCT solvers (one block, rmhd_run with fused = 0)"; return -1; }
       if (cfg->fused) { g_driver_error = std::string(who) + ": the fused limiter and the one-kernel stage have their LO solver and clip + scale built in (fused must be 0)"; return -1; }
       if (cfg->ps) { g_driver_error = std::string(who) + ": product remap (ps) is not implemented for the DiscreteUpwind / FluxBasedFCT solvers"; return -1; }
@@ -620,6 +621,11 @@ extern "C" int rmhd_run_rank(const rmhd_config *cfg, const char *comm_id_file, i
    CaseData cd;
    const std::string err = build_case(cc, cd);
    if (!err.empty()) { g_driver_error = err; return -1; }
+   if (cc.lo_type == 2 && cd.dim == 3 && cd.order >= 4)
+   {
+      g_driver_error = "lo_type 2 (-lo 2): order " + std::to_string(cd.order) + " in 3-D is not supported: the element's dense matrices must fit the LDS (orders 1 to 3 in 3-D, 1 to 6 in 2-D)";
+      return -1;
+   }
 
    rmh_layout L;
    L.dim = cd.dim; // (2: the reference's quadrilateral lattices, one rank -- build_case_2d)
@@ -718,6 +724,7 @@ extern "C" int rmhd_run_rank(const rmhd_config *cfg, const char *comm_id_file, i
       LOSolver *lo_solver = nullptr;
       if (cc.lo_type == 5) { lo_solver = new MassBasedAvg(pfes, *ho_solver, nullptr); }
       else if (cc.lo_type == 1) { lo_solver = new DiscreteUpwind(pfes, cd.exec_mode == 1); } // remhos.cpp:931-936
+      else if (cc.lo_type == 2) { lo_solver = new DiscreteUpwind(pfes, cd.exec_mode == 1, true); } // remhos.cpp:937-942
       else if (cc.lo_type == 3) { lo_solver = new PAResidualDistribution(pfes); }
       else { lo_solver = new PAResidualDistributionSubcell(pfes); }
       double dt = cd.dt;

@@ -305,7 +305,7 @@ static std::string build_case_2d(const CaseConfig &cfg, CaseData &out)
    if (cfg.order < 1 || cfg.order > 6) { return "order must be in 1..6"; }
    if (cfg.px != 1 || cfg.py != 1 || cfg.pz != 1 || cfg.rank != 0 || cfg.self_wrap != 0) { return "dim = 2 runs on one rank"; }
    if (cfg.rs_extra[0] || cfg.rs_extra[1] || cfg.rs_extra[2]) { return "dim = 2: no rs_extra"; }
-   if (cfg.lo_type != 1 && cfg.lo_type != 3 && cfg.lo_type != 4 && cfg.lo_type != 5) { return "lo_type must be 1, 3, 4 or 5"; }
+   if (cfg.lo_type != 1 && cfg.lo_type != 2 && cfg.lo_type != 3 && cfg.lo_type != 4 && cfg.lo_type != 5) { return "lo_type must be 1, 2, 3, 4 or 5"; }
    if (const std::string e = check_problem(cfg.problem); !e.empty()) { return e; }
    const std::vector<double> verts = refine(coarse, cfg.rs);
    const int N = (int)verts.size() - 1, p = cfg.order, D = p + 1, problem = cfg.problem;
@@ -460,7 +460,7 @@ std::string build_case(const CaseConfig &cfg, CaseData &out)
    if (cfg.px < 1 || cfg.py < 1 || cfg.pz < 1) { return "bad partition"; }
    const int nranks = cfg.px * cfg.py * cfg.pz;
    if (cfg.rank < 0 || cfg.rank >= nranks) { return "bad rank"; }
-   if (cfg.lo_type != 1 && cfg.lo_type != 3 && cfg.lo_type != 4 && cfg.lo_type != 5) { return "lo_type must be 1, 3, 4 or 5"; }
+   if (cfg.lo_type != 1 && cfg.lo_type != 2 && cfg.lo_type != 3 && cfg.lo_type != 4 && cfg.lo_type != 5) { return "lo_type must be 1, 2, 3, 4 or 5"; }
    if (const std::string e = check_problem(cfg.problem); !e.empty()) { return e; }
 
    // per direction: -rs levels plus rs_extra[d] more (0 in the reference's meshes; the weak-scaling lattices of
