@@ -148,6 +148,18 @@ public:
    void CalcHOSolution(const Vector &u, Vector &du) const override;
 };
 
+// remhos_ho.hpp:70-85, remhos_ho.cpp:131-187 (-ho 1): du = 0, then at most 20 updates du -= (M du - rhs) / m_L with the consistent
+// element mass M, its lumping m_L and rhs = k u + LinearFluxLumping (alpha = 1), stopped by the global residual norm (1e-4).  The
+// mass and convection forms, the lumped mass vector and the Assembly object of the reference's constructor have no counterpart:
+// the kernels apply M and k by sum factorisation on the mesh of the operator's time and read the context's lumped mass
+// (rmh_ho_neumann).  One rank.
+class NeumannHOSolver : public HOSolver
+{
+public:
+   NeumannHOSolver(ParFiniteElementSpace &space) : HOSolver(space) {}
+   void CalcHOSolution(const Vector &u, Vector &du) const override;
+};
+
 // Low-Order Solver (remhos_lo.hpp:28-44)
 class LOSolver
 {

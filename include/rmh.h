@@ -78,7 +78,7 @@ typedef struct {
  * BASELINE configs[0]'s mesh family.  Layout: x0 / vel [ne][2][9] (node a = ax + 3*ay), face_nbr [ne][4] (f = 2*c + side),
  * `stencil27` = the 3 x 3 element stencil [ne][9] (entry (ox+1) + 3*(oy+1)), ne_ghost = 0, subcell_vel [ne][2][(p+1)^2] or NULL; E-vectors
  * carry (p+1)^2 doubles per element; Q = p + 2 quadrature points per direction.  Entry points: rmh_setup,
- * rmh_ho_apply, rmh_lumped_mass, rmh_compute_lumped_mass, rmh_lo_massavg, rmh_lo_rd, rmh_lo_rdsubcell, rmh_lo_upwind, rmh_lo_upwind_prec, rmh_elem_minmax, rmh_bounds, rmh_fct_clipscale, rmh_fct_projection, rmh_fct_fluxbased,
+ * rmh_ho_apply, rmh_ho_neumann, rmh_last_neumann, rmh_lumped_mass, rmh_compute_lumped_mass, rmh_lo_massavg, rmh_lo_rd, rmh_lo_rdsubcell, rmh_lo_upwind, rmh_lo_upwind_prec, rmh_elem_minmax, rmh_bounds, rmh_fct_clipscale, rmh_fct_projection, rmh_fct_fluxbased,
  * rmh_limit_fused, rmh_limit_fused_lo, rmh_stage_fused (the whole rank: HO kernel, RD solver for lo 3 / 4 and the fused limiter run
  * as a sequence inside the library; no tokens), the mass-rule / bounds-type / dt-control setters and getters, timers.  Everything
  * else (element ranges of a stage, product fields, exchange) returns RMH_ERR_INVALID for a 2-D context. */
@@ -232,6 +232,19 @@ int rmh_comm_count(rmh_ctx *ctx, int *nranks);
  * du = M^-1 (K_vol + K_face) u with an element-local, tightly converged mass solve.
  * Also refreshes the lumped mass vector (remhos.cpp:1632) and the element extrema of u. */
 int rmh_ho_apply(rmh_ctx *ctx, const double *u, double *du);
+
+/* HOSolver::CalcHOSolution, NeumannHOSolver (-ho 1; remhos_ho.hpp:70-85, remhos_ho.cpp:131-187, remhos.cpp:914-917):
+ * rhs = K_vol u + sum_F PhiF^T diag(s_F) PhiF (u^nbr - u) -- the right-hand side of rmh_ho_apply -- then du = 0 and at most 20
+ * updates du -= (M du - rhs) / m_L, stopping BEFORE the first update whose GLOBAL residual norm ||M du - rhs||_2 is <= 1e-4; no
+ * check behind the 20th update.  The reference's stopping iteration is reproduced, not a converged solve (DESIGN.md section
+ * 3.16).  Four launches on the context's stream, no host synchronisation, no atomics; the same bits from run to run.  Forms the
+ * context's lumped mass unless an HO / RD call has left it since the last rmh_setup, refreshes the element extrema of u and
+ * leaves both current like rmh_ho_apply.  Timers: t[0] the right-hand side, t[1] the iteration.  dim = 3 and dim = 2, every
+ * order.  A context with ghost elements returns RMH_ERR_INVALID (the global norm would need a reduction over the ranks).
+ * rmh_last_neumann: the updates applied by the last call (0 .. 20) and the residual norms of its checks; entries that were not
+ * evaluated are NaN.  Synchronises. */
+int rmh_ho_neumann(rmh_ctx *ctx, const double *u, double *du);
+int rmh_last_neumann(rmh_ctx *ctx, int *updates, double norms[20]);
 
 /* Lumped mass M_HO * 1 at the pseudo-time of the last rmh_setup (remhos.cpp:719-727, 1625-1632).
  * rmh_lumped_mass returns the ctx-owned device vector written by rmh_ho_apply;

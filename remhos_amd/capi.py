@@ -14,7 +14,7 @@ LIB_PATH = os.path.join(_HERE, "librmh.so")
 # every symbol include/rmh.h declares (tests/test_capi_symbols.py checks the header against this)
 SYMBOLS = [
     "rmh_create", "rmh_destroy", "rmh_last_error", "rmh_version", "rmh_set_stream", "rmh_stream_create_reserving", "rmh_stream_destroy", "rmh_batch_order", "rmh_setup",
-    "rmh_set_ghost_u", "rmh_set_ghost_minmax", "rmh_halo_pack", "rmh_ho_apply", "rmh_lumped_mass",
+    "rmh_set_ghost_u", "rmh_set_ghost_minmax", "rmh_halo_pack", "rmh_ho_apply", "rmh_ho_neumann", "rmh_last_neumann", "rmh_lumped_mass",
     "rmh_compute_lumped_mass", "rmh_lo_massavg", "rmh_lo_rdsubcell", "rmh_lo_rd", "rmh_elem_minmax", "rmh_bounds",
     "rmh_fct_clipscale", "rmh_fct_projection", "rmh_lo_upwind", "rmh_lo_upwind_prec", "rmh_fct_fluxbased", "rmh_limit_fused", "rmh_limit_fused_lo", "rmh_stage_fused", "rmh_stage_fused_range", "rmh_stage_fused_chain",
     "rmh_halo_pack_records", "rmh_set_ghost_records", "rmh_timers", "rmh_reset_timers", "rmh_enable_timers",
@@ -115,6 +115,8 @@ def load_library(path: str | None = None) -> C.CDLL:
     lib.rmh_fct_projection.argtypes = [p, p, p, p, p, p, p, d, p]
     lib.rmh_lo_upwind.argtypes = [p, p, p]
     lib.rmh_lo_upwind_prec.argtypes = [p, p, p]
+    lib.rmh_ho_neumann.argtypes = [p, p, p]
+    lib.rmh_last_neumann.argtypes = [p, C.POINTER(i), C.POINTER(d * 20)]
     lib.rmh_fct_fluxbased.argtypes = [p, p, p, p, p, p, p, d, p]
     lib.rmh_limit_fused.argtypes = [p, p, p, d, p, p, d, d, d, p]
     lib.rmh_limit_fused_lo.argtypes = [p, p, p, p, d, p, p, d, d, d, p]
@@ -286,6 +288,18 @@ class Context:
     def lo_upwind_prec(self, u, du_lo):
         """DiscreteUpwind with the preconditioned matrix M_L M^-1 C (-lo 2) at the geometry of the last setup(t)"""
         self._check(self.lib.rmh_lo_upwind_prec(self.h, _ptr(u), _ptr(du_lo)))
+
+    def ho_neumann(self, u, du):
+        """NeumannHOSolver (-ho 1) at the geometry of the last setup(t): at most 20 lumped-mass updates, the reference's global
+        stopping test"""
+        self._check(self.lib.rmh_ho_neumann(self.h, _ptr(u), _ptr(du)))
+
+    def last_neumann(self):
+        """(updates applied, the 20 residual norms -- NaN where a check was not evaluated) of the last ho_neumann; synchronises"""
+        n = C.c_int(0)
+        norms = (C.c_double * 20)()
+        self._check(self.lib.rmh_last_neumann(self.h, C.byref(n), C.byref(norms)))
+        return n.value, list(norms)
 
     def fct_fluxbased(self, u, m, du_ho, du_lo, u_min, u_max, dt, du):
         """FluxBasedFCT (-fct 1, one iteration) at the geometry of the last setup(t); m is the lumped mass"""

@@ -1,7 +1,7 @@
 // remhos_amd -- command-line front end of the single-GPU driver (rmhd_run), accepting the subset of
 // the reference's flags that select the hot path (remhos.cpp:249-334) and printing the same report
 // lines (remhos.cpp:1423-1428, 1938-1952):
-//   remhos_amd -m periodic-cube -p 10 -rs 4 -o 3 -dt -1 -tf 0.5 -ms 20 -ho 3 -lo 5 -fct 2 -pa [-bt 1 -dtc 1]   (-fct 4: element FCT projection, -lo 1 / -lo 2 / -fct 1: DiscreteUpwind / its preconditioned form / FluxBasedFCT; granular sequence)
+//   remhos_amd -m periodic-cube -p 10 -rs 4 -o 3 -dt -1 -tf 0.5 -ms 20 -ho 3 -lo 5 -fct 2 -pa [-bt 1 -dtc 1]   (-fct 4: element FCT projection, -ho 1 / -lo 1 / -lo 2 / -fct 1: NeumannHOSolver / DiscreteUpwind / its preconditioned form / FluxBasedFCT; granular sequence)
 #include "../../include/rmh_driver.h"
 
 #include <cstdio>
@@ -62,9 +62,17 @@ int main(int argc, char **argv)
       else if (a == "-tile") { c.tile_rows = std::atoi(next()); } // element numbering of the case builder (rmh_driver.h)
       else { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return 1; }
    }
-   if ((ho != 2 && ho != 3) || (fct != 1 && fct != 2 && fct != 4) || c.lo_type < 1 || c.lo_type > 5)
+   if ((ho != 1 && ho != 2 && ho != 3) || (fct != 1 && fct != 2 && fct != 4) || c.lo_type < 1 || c.lo_type > 5)
    {
-      std::fprintf(stderr, "remhos_amd implements -ho 2|3, -lo 3|4|5, -fct 2|4, -bt 0|1, -dtc 0|1 (the hot path of SURVEY.md section 8), and -lo 1, -lo 2, -fct 1 (DiscreteUpwind, preconditioned DiscreteUpwind, FluxBasedFCT: the reference's -lo 1|2|3|4|5, -fct 1|2|4)\n");
+      std::fprintf(stderr, "remhos_amd implements -ho 2|3, -lo 3|4|5, -fct 2|4, -bt 0|1, -dtc 0|1 (the hot path of SURVEY.md section 8), and -ho 1, -lo 1, -lo 2, -fct 1 (NeumannHOSolver, DiscreteUpwind, preconditioned DiscreteUpwind, FluxBasedFCT: the reference's -ho 1|2|3, -lo 1|2|3|4|5, -fct 1|2|4)\n");
+      return 1;
+   }
+   // -ho 1 runs with the solver classes only.  Here it is taken where the options already say so -- beside -lo 2 (the reference's
+   // regression method) or -fct 4, or with -unfused beside -lo 3|4|5 -- and the one-kernel default is never switched off silently for
+   // it.  Beside -lo 1 / -fct 1 it goes through rmhd_run (ho_type = 1), not through this front end.
+   if (ho == 1 && (c.lo_type == 1 || fct == 1 || (c.fused && c.lo_type != 2 && fct != 4)))
+   {
+      std::fprintf(stderr, "remhos_amd implements -ho 1 (NeumannHOSolver) with the solver classes: beside -lo 2 or -fct 4, or with -unfused beside -lo 3|4|5 -fct 2; not beside -lo 1 or -fct 1 (rmhd_run with ho_type = 1 takes those)\n");
       return 1;
    }
    c.ho_type = ho;

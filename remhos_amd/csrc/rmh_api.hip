@@ -8,6 +8,7 @@
 #include "rmh_efp.hpp"
 #include "rmh_upwind.hpp"
 #include "rmh_pdu.hpp"
+#include "rmh_neumann.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -636,7 +637,7 @@ void rmh_destroy(rmh_ctx *c)
    if (!c) { return; }
    (void)hipSetDevice(c->device);
    exchange_free(c);
-   void *bufs[] = {c->d_x0, c->d_vel, c->d_x0h, c->d_velh, c->d_tab, c->d_subvel, c->d_subx0, c->d_subvmid, c->d_fgeo, c->d_face_rows, c->d_m, c->d_scr_ho, c->d_scr_lo, c->d_xe_min, c->d_xe_max, c->d_xe_min2, c->d_xe_max2, c->d_nbr, c->d_st27, c->d_cg, c->d_dt_est, c->d_viol};
+   void *bufs[] = {c->d_x0, c->d_vel, c->d_x0h, c->d_velh, c->d_tab, c->d_subvel, c->d_subx0, c->d_subvmid, c->d_fgeo, c->d_face_rows, c->d_m, c->d_scr_ho, c->d_scr_lo, c->d_xe_min, c->d_xe_max, c->d_xe_min2, c->d_xe_max2, c->d_nbr, c->d_st27, c->d_cg, c->d_dt_est, c->d_viol, c->d_nm_rhs, c->d_nm_wdet, c->d_nm_part, c->d_nm_norms, c->d_nm_ctl};
    for (void *b : bufs) { (void)hipFree(b); }
    for (int b = 0; b < 4; b++)
    {
@@ -1040,6 +1041,95 @@ int rmh_lo_upwind_prec(rmh_ctx *c, const double *u, double *du_lo)
    if (rc) { return rc; }
    RMH_HIP(hipGetLastError());
    return timer_end(c, 2, ep);
+}
+
+namespace
+{
+extern "C++" template <int P, int DIM>
+void launch_neumann_rhs(rmh_ctx *c, const UpwArgs &a, const double *u)
+{
+   hipLaunchKernelGGL((neumann_rhs_kernel<P, DIM>), dim3(c->ne), dim3(EfpCfg<P, DIM>::NT), 0, c->stream, a, u, c->d_nm_rhs, c->d_nm_wdet);
+}
+
+// first pass (20 updates, the elements' residual norms), the global norms and the stopping check K, second pass (K - 1 updates)
+extern "C++" template <int P, int DIM>
+void launch_neumann_iter(rmh_ctx *c, double *du)
+{
+   hipLaunchKernelGGL((neumann_iter_kernel<P, DIM>), dim3(c->ne), dim3(EfpCfg<P, DIM>::NT), 0, c->stream,
+                      (const double *)c->d_tab, (const double *)c->d_nm_wdet, (const double *)c->d_nm_rhs, (const double *)c->d_m,
+                      (const int *)c->d_nm_ctl, c->d_nm_part, du);
+   hipLaunchKernelGGL(neumann_norms_kernel, dim3(1), dim3(NEUMANN_NORMS_NT), 0, c->stream, (const double *)c->d_nm_part, c->ne,
+                      c->d_nm_norms, c->d_nm_ctl);
+   hipLaunchKernelGGL((neumann_iter_kernel<P, DIM>), dim3(c->ne), dim3(EfpCfg<P, DIM>::NT), 0, c->stream,
+                      (const double *)c->d_tab, (const double *)c->d_nm_wdet, (const double *)c->d_nm_rhs, (const double *)c->d_m,
+                      (const int *)c->d_nm_ctl + 1, (double *)nullptr, du);
+}
+} // namespace
+
+int rmh_ho_neumann(rmh_ctx *c, const double *u, double *du)
+{
+   if (!c || !u || !du) { return fail(RMH_ERR_INVALID, "null argument"); }
+   if (c->ng > 0)
+   {
+      return fail(RMH_ERR_INVALID, "rmh_ho_neumann (-ho 1): contexts with ghost elements are not supported (the global residual norm would need a reduction over the ranks: the solver runs on one rank)");
+   }
+   RMH_ENTER(c);
+   if (!c->d_nm_ctl)
+   {
+      const int ctl0[NEUMANN_NCTL] = {NEUMANN_MAX_UPDATES, -1, 0, 0};
+      RMH_HIP(hipMalloc((void **)&c->d_nm_rhs, (size_t)c->ne * c->ndof * sizeof(double)));
+      const int q1 = c->p + (c->dim == 3 ? 3 : 2); // quadrature points a direction (EfpCfg)
+      RMH_HIP(hipMalloc((void **)&c->d_nm_wdet, (size_t)c->ne * (c->dim == 3 ? q1 * q1 * q1 : q1 * q1) * sizeof(double)));
+      RMH_HIP(hipMalloc((void **)&c->d_nm_part, (size_t)NEUMANN_MAX_UPDATES * c->ne * sizeof(double)));
+      RMH_HIP(hipMalloc((void **)&c->d_nm_norms, NEUMANN_MAX_UPDATES * sizeof(double)));
+      int *ctl = nullptr;
+      RMH_HIP(hipMalloc((void **)&ctl, sizeof(ctl0)));
+      c->d_nm_ctl = ctl;
+      RMH_HIP(hipMemcpy(ctl, ctl0, sizeof(ctl0), hipMemcpyHostToDevice));
+   }
+   // the lumped mass of this geometry: formed here unless an HO / RD call has left it since the last rmh_setup; the element
+   // extrema of u go with it (what ho_done promises to rmh_limit_fused)
+   if (!c->ho_done)
+   {
+      const int rc = rmh_compute_lumped_mass(c, c->t, c->d_m);
+      if (rc) { return rc; }
+   }
+   {
+      const int rc = rmh_elem_minmax(c, u, c->d_xe_min, c->d_xe_max);
+      if (rc) { return rc; }
+   }
+   const UpwArgs a = upwind_args(c);
+   EventPair ep;
+   int rc = timer_begin(c, 0, ep);
+   if (rc) { return rc; }
+   if (c->dim == 2) { RMH_DISPATCH(c, (launch_neumann_rhs<P, 2>(c, a, u))); }
+   else { RMH_DISPATCH(c, (launch_neumann_rhs<P, 3>(c, a, u))); }
+   RMH_HIP(hipGetLastError());
+   rc = timer_end(c, 0, ep);
+   if (rc) { return rc; }
+   rc = timer_begin(c, 1, ep);
+   if (rc) { return rc; }
+   if (c->dim == 2) { RMH_DISPATCH(c, (launch_neumann_iter<P, 2>(c, du))); }
+   else { RMH_DISPATCH(c, (launch_neumann_iter<P, 3>(c, du))); }
+   RMH_HIP(hipGetLastError());
+   rc = timer_end(c, 1, ep);
+   c->ho_done = true;
+   extrema_dropped(c);
+   return rc;
+}
+
+int rmh_last_neumann(rmh_ctx *c, int *updates, double norms[20])
+{
+   if (!c || !updates || !norms) { return fail(RMH_ERR_INVALID, "null argument"); }
+   if (!c->d_nm_ctl) { return fail(RMH_ERR_STATE, "rmh_last_neumann: no rmh_ho_neumann call on this context"); }
+   RMH_ENTER(c);
+   RMH_HIP(hipStreamSynchronize(c->stream));
+   int ctl[NEUMANN_NCTL];
+   RMH_HIP(hipMemcpy(ctl, c->d_nm_ctl, sizeof(ctl), hipMemcpyDeviceToHost));
+   RMH_HIP(hipMemcpy(norms, c->d_nm_norms, NEUMANN_MAX_UPDATES * sizeof(double), hipMemcpyDeviceToHost));
+   for (int k = std::max(0, ctl[3]); k < NEUMANN_MAX_UPDATES; k++) { norms[k] = std::nan(""); } // (checks that were not evaluated)
+   *updates = ctl[2];
+   return RMH_OK;
 }
 
 int rmh_fct_fluxbased(rmh_ctx *c, const double *u, const double *m, const double *du_ho, const double *du_lo,

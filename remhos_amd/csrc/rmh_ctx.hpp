@@ -75,6 +75,10 @@ struct rmh_ctx
    double *d_dt_est = nullptr; // running minimum of UpdateTimeStepEstimate; null while dt control is off
    bool dt_control = false;
    unsigned long long *d_viol = nullptr; // verdict words of rmh_check_violation (made on first use)
+   // scratch of rmh_ho_neumann (made on first use): the right-hand side [ne][ndof], w detJ at the quadrature points [ne][Q^dim],
+   // the elements' squared residual norms [20][ne], the 20 global norms and the control words of rmh_neumann.hpp
+   double *d_nm_rhs = nullptr, *d_nm_wdet = nullptr, *d_nm_part = nullptr, *d_nm_norms = nullptr;
+   int *d_nm_ctl = nullptr;
    int lo_type = 5;    // LO solver inside rmh_stage_fused: 5 mass-based average, 4 subcell residual distribution
    // stopwatches (TimingData, remhos_tools.hpp:52-64)
    bool timers_on = false;

@@ -229,6 +229,12 @@ void ElementFCTProjection::CalcFCTProduct(const ParGridFunction &, const Vector 
    RMH_VERIFY(false, "Product remap (-ps) is not implemented for ElementFCTProjection (-fct 4)");
 }
 
+void NeumannHOSolver::CalcHOSolution(const Vector &u, Vector &du) const
+{
+   // remhos_ho.cpp:136-187 (the assembly-level check of :138-139 is the driver's: ho_type 1 with pa is refused)
+   RMH_CALL(rmh_ho_neumann(pfes.Ctx(), u.Read(), du.Write()));
+}
+
 void DiscreteUpwind::CalcLOSolution(const Vector &u, Vector &du) const
 {
    // remhos_lo.cpp:43-100 (D is rebuilt on the mesh of the operator's time by the kernel: update_D)
@@ -255,6 +261,17 @@ void FluxBasedFCT::CalcFCTProduct(const ParGridFunction &, const Vector &, const
 static int check_fct_type(const rmhd_config *cfg, bool partitioned)
 {
    const int fct = cfg->fct_type;
+   // -ho: 0 means 3; no other value may fall through to the local inverse
+   if (cfg->ho_type < 0 || cfg->ho_type > 3) { g_driver_error = "ho_type must be 1 (Neumann iteration), 2 (CG) or 3 (local inverse; 0 means 3): got " + std::to_string(cfg->ho_type); return -1; }
+   if (cfg->ho_type == 1)
+   {
+      // NeumannHOSolver (-ho 1) runs through the granular solver sequence on one block: its stopping test is a global norm
+      if (partitioned || cfg->px * cfg->py * cfg->pz > 1) { g_driver_error = "ho_type 1 (-ho 1): partitioned runs are not built for the Neumann HO solver (one block, rmhd_run with fused = 0)"; return -1; }
+      if (cfg->self_wrap) { g_driver_error = "ho_type 1 (-ho 1): a self-wrapped block (self_wrap) has ghost elements, which rmh_ho_neumann does not take"; return -1; }
+      if (cfg->fused) { g_driver_error = "ho_type 1 (-ho 1): the one-kernel stage has the local inverse built in (fused must be 0)"; return -1; }
+      if (cfg->pa) { g_driver_error = "ho_type 1 (-ho 1) with -pa: PA for DG is not supported for Neummann Solver"; return -1; } // remhos_ho.cpp:138-139
+      if (cfg->ps) { g_driver_error = "ho_type 1 (-ho 1) with -ps: product remap (ps) is not built for the Neumann HO solver"; return -1; }
+   }
    if (fct != 0 && fct != 1 && fct != 2 && fct != 4) { g_driver_error = "fct_type must be 1 (flux-based FCT), 2 (clip + scale; 0 means 2) or 4 (element FCT projection)"; return -1; }
    if (fct == 1 || cfg->lo_type == 1 || cfg->lo_type == 2)
    {
@@ -719,7 +736,8 @@ extern "C" int rmhd_run_rank(const rmhd_config *cfg, const char *comm_id_file, i
       DofInfo dofs(pfes);
       // solver factory of remhos.cpp:912-925, 927-995 for the options on the path
       HOSolver *ho_solver = nullptr;
-      if (cfg->ho_type == 2) { ho_solver = new CGHOSolver(pfes); }
+      if (cfg->ho_type == 1) { ho_solver = new NeumannHOSolver(pfes); } // remhos.cpp:914-917
+      else if (cfg->ho_type == 2) { ho_solver = new CGHOSolver(pfes); }
       else { ho_solver = new LocalInverseHOSolver(pfes, cfg->pa != 0); }
       LOSolver *lo_solver = nullptr;
       if (cc.lo_type == 5) { lo_solver = new MassBasedAvg(pfes, *ho_solver, nullptr); }

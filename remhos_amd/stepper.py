@@ -19,6 +19,10 @@ class Stepper:
     def __init__(self, lib, case, device="cuda:0", dist=None, fused=True, one_kernel=True, overlap=True):
         self.case = case
         self.lib = lib
+        if getattr(case.cfg, "ho_type", 3) == 1:
+            # NeumannHOSolver stops on a global norm: it runs through the solver classes of the driver (fused = 0), not here
+            raise ValueError("ho_type 1 (-ho 1, Neumann iteration) is not built into the stepper's stages: run it through "
+                             "rmhd_run with fused = 0")
         if hasattr(lib, "rmhd_axpby") and not lib.rmhd_axpby.argtypes:  # (a library handle that did not go through case.bind_driver)
             import ctypes as _C
             lib.rmhd_axpby.argtypes = [_C.c_double, _C.c_void_p, _C.c_double, _C.c_void_p, _C.c_void_p, _C.c_longlong, _C.c_void_p]
