@@ -9,6 +9,7 @@
 #include "rmh_upwind.hpp"
 #include "rmh_pdu.hpp"
 #include "rmh_neumann.hpp"
+#include "rmh_product2d.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -355,7 +356,7 @@ int launch_stage_fused(rmh_ctx *c, const double *u, double dt, const double *x_b
 
 // entry points that exist for hexahedra only
 #define RMH_3D_ONLY(c, name)                                                                                              \
-   if ((c)->dim != 3) { return fail(RMH_ERR_INVALID, name ": not available for dim = 2 (HO solver and granular limiter sequence only)"); }
+   if ((c)->dim != 3) { return fail(RMH_ERR_INVALID, name ": not available for dim = 2 (HO solver, granular limiter sequence and product remap only)"); }
 
 // dim = 2: nodes [ne][2][9], face_nbr [ne][4]; the caller's 3 x 3 element stencil [ne][9] becomes the middle layer of the
 // 27-entry table that the bounds kernels read (no neighbours along z)
@@ -1168,11 +1169,18 @@ int rmh_product_ratio(rmh_ctx *c, const double *us, const double *u, double *s, 
                       unsigned char *active_dofs)
 {
    if (!c || !u || !active_el || !active_dofs || ((us != nullptr) != (s != nullptr))) { return fail(RMH_ERR_INVALID, "null argument"); }
-   RMH_3D_ONLY(c, "rmh_product_ratio");
    RMH_ENTER(c);
    extrema_dropped(c);
-   RMH_DISPATCH(c, hipLaunchKernelGGL((product_ratio_kernel<P>), dim3(c->ne), dim3(KCfg<P>::NT), 0, c->stream, us, u, s,
-                                      active_el, active_dofs));
+   if (c->dim == 2)
+   {
+      RMH_DISPATCH(c, hipLaunchKernelGGL((product_ratio2d_kernel<P>), dim3(P2Cfg<P>::grid(c->ne)), dim3(P2Cfg<P>::NT), 0, c->stream,
+                                         us, u, s, active_el, active_dofs, c->ne));
+   }
+   else
+   {
+      RMH_DISPATCH(c, hipLaunchKernelGGL((product_ratio_kernel<P>), dim3(c->ne), dim3(KCfg<P>::NT), 0, c->stream, us, u, s,
+                                         active_el, active_dofs));
+   }
    RMH_HIP(hipGetLastError());
    return RMH_OK;
 }
@@ -1181,10 +1189,17 @@ int rmh_elem_minmax_masked(rmh_ctx *c, const double *u, const unsigned char *act
                            double *xe_min, double *xe_max)
 {
    if (!c || !u || !active_el || !active_dofs || !xe_min || !xe_max) { return fail(RMH_ERR_INVALID, "null argument"); }
-   RMH_3D_ONLY(c, "rmh_elem_minmax_masked");
    RMH_ENTER(c);
-   RMH_DISPATCH(c, hipLaunchKernelGGL((elem_minmax_masked_kernel<P>), dim3(c->ne), dim3(KCfg<P>::NT), 0, c->stream, u,
-                                      active_el, active_dofs, xe_min, xe_max));
+   if (c->dim == 2)
+   {
+      RMH_DISPATCH(c, hipLaunchKernelGGL((elem_minmax_masked2d_kernel<P>), dim3(P2Cfg<P>::grid(c->ne)), dim3(P2Cfg<P>::NT), 0,
+                                         c->stream, u, active_el, active_dofs, xe_min, xe_max, c->ne));
+   }
+   else
+   {
+      RMH_DISPATCH(c, hipLaunchKernelGGL((elem_minmax_masked_kernel<P>), dim3(c->ne), dim3(KCfg<P>::NT), 0, c->stream, u,
+                                         active_el, active_dofs, xe_min, xe_max));
+   }
    RMH_HIP(hipGetLastError());
    return RMH_OK;
 }
@@ -1197,15 +1212,22 @@ int rmh_fct_product(rmh_ctx *c, const double *us, const double *m, const double 
    {
       return fail(RMH_ERR_INVALID, "null argument");
    }
-   RMH_3D_ONLY(c, "rmh_fct_product");
    if (!(dt > 0.0)) { return fail(RMH_ERR_INVALID, "dt must be positive"); }
    RMH_ENTER(c);
    extrema_dropped(c);
    EventPair ep;
    int rc = timer_begin(c, 3, ep);
    if (rc) { return rc; }
-   RMH_DISPATCH(c, hipLaunchKernelGGL((fct_product_kernel<P>), dim3(c->ne), dim3(KCfg<P>::NT), 0, c->stream, us, m, d_us_ho,
-                                      s_min, s_max, u_new, active_el, active_dofs, dt, d_us));
+   if (c->dim == 2)
+   {
+      RMH_DISPATCH(c, hipLaunchKernelGGL((fct_product2d_kernel<P>), dim3(P2Cfg<P>::grid(c->ne)), dim3(P2Cfg<P>::NT), 0, c->stream,
+                                         us, m, d_us_ho, s_min, s_max, u_new, active_el, active_dofs, dt, d_us, c->ne));
+   }
+   else
+   {
+      RMH_DISPATCH(c, hipLaunchKernelGGL((fct_product_kernel<P>), dim3(c->ne), dim3(KCfg<P>::NT), 0, c->stream, us, m, d_us_ho,
+                                         s_min, s_max, u_new, active_el, active_dofs, dt, d_us));
+   }
    RMH_HIP(hipGetLastError());
    return timer_end(c, 3, ep);
 }

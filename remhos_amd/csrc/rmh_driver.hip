@@ -644,6 +644,16 @@ extern "C" int rmhd_run_rank(const rmhd_config *cfg, const char *comm_id_file, i
       return -1;
    }
 
+   if (cfg->ps)
+   {
+      // what product remap (-ps) asks of the other options, in 3-D and in 2-D alike -- said before a device context exists
+      const char *why = nullptr;
+      if (cd.exec_mode != 1) { why = "Products are processed only in remap mode."; }                          // remhos.cpp:1713
+      else if (cfg->dt_control) { why = "Automatic time step is not implemented for product remap."; }        // remhos.cpp:1714
+      else if (cc.lo_type != 5) { why = "product remap is built for -lo 5 (what the fused limiter kernel takes)"; }
+      if (why) { g_driver_error = why; return -1; }
+   }
+
    rmh_layout L;
    L.dim = cd.dim; // (2: the reference's quadrilateral lattices, one rank -- build_case_2d)
    L.order = cd.order;
@@ -757,9 +767,6 @@ extern "C" int rmhd_run_rank(const rmhd_config *cfg, const char *comm_id_file, i
       const int ode_type = cfg->ode_solver ? cfg->ode_solver : 3;
       const bool idp = ode_type > 10;
       RMH_VERIFY(ode_type == 3 || ode_type == 11 || ode_type == 12 || ode_type == 13, "-s must be 3, 11, 12 or 13");
-      RMH_VERIFY(!ps || cd.exec_mode == 1, "Products are processed only in remap mode.");                         // remhos.cpp:1713
-      RMH_VERIFY(!ps || !cfg->dt_control, "Automatic time step is not implemented for product remap.");           // remhos.cpp:1714
-      RMH_VERIFY(!ps || cc.lo_type == 5, "product remap is built for -lo 5 (what the fused limiter kernel takes)");
       // fused = 1: one kernel per RK stage (rmh_stage_fused with the LO solver and the mass tolerance of the options)
       const bool fused = cfg->fused != 0 && !ps && !idp;
       if (fused)
