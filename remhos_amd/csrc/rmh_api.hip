@@ -48,7 +48,7 @@ inline void extrema_dropped(rmh_ctx *c)
 
 int timers_resolve(rmh_ctx *c);
 
-int timer_begin(rmh_ctx *c, int bucket, EventPair &ep)
+int timer_begin(rmh_ctx *c, EventPair &ep)
 {
    if (!c->timers_on) { return 0; }
    if (c->pool.empty())
@@ -62,7 +62,6 @@ int timer_begin(rmh_ctx *c, int bucket, EventPair &ep)
       c->pool.pop_back();
    }
    RMH_HIP(hipEventRecord(ep.a, c->stream));
-   (void)bucket;
    return 0;
 }
 
@@ -92,6 +91,17 @@ int timers_resolve(rmh_ctx *c)
    return 0;
 }
 
+// launch() under the stopwatch of a bucket: start event, launch, the launch error, stop event; the first failure is returned
+template <typename F>
+int timed(rmh_ctx *c, int bucket, F &&launch)
+{
+   EventPair ep;
+   if (int rc = timer_begin(c, ep)) { return rc; }
+   if (int rc = launch()) { return rc; }
+   RMH_HIP(hipGetLastError());
+   return timer_end(c, bucket, ep);
+}
+
 template <typename T>
 int upload(T **dst, const T *src, size_t n)
 {
@@ -104,8 +114,8 @@ int upload(T **dst, const T *src, size_t n)
 template <int P>
 static int stage_batch_elements(const rmh_ctx *c)
 {
-   if (c->lo_type == 4 || c->lo_type == 3) { return K2Cfg<(P >= 2 ? P : 2), true, true>::NB; }
-   return K2Cfg<P>::NB;
+   if (c->lo_type == 4 || c->lo_type == 3) { return K2For<(P >= 2 ? P : 2), 3>::NB; }
+   return K2For<P, 1>::NB;
 }
 
 // Chunk of the XCD-aware batch order of ho_kernel2 for a launch of nblk batches of NB elements (HoArgs::xcd_chunk, xcd_weave):
@@ -168,11 +178,15 @@ int ensure_face_table(rmh_ctx *c)
    return 0;
 }
 
-template <int P, int MODE>
-int launch_ho(rmh_ctx *c, const double *u, double *du, double *m, double t)
+// RD solver of the kernels that have one: 1 subcell fluctuations (lo 4), 0 plain PAResidualDistribution (lo 3)
+inline int rd_subcell_of(const rmh_ctx *c) { return c->lo_type == 3 ? 0 : 1; }
+
+// what every ho_kernel2 launch takes from the context; the rest as the granular launches (launch_ho) want it: the whole rank, overlap
+// bounds, no RK update, no step estimate, batches in ascending order.  u, du, m and t are the launcher's; the face table and the
+// batch order are filled in by launch_ho2.
+HoArgs ho_args(const rmh_ctx *c)
 {
-   HoArgs a;
-   a.u = u;
+   HoArgs a = {};
    a.u_ghost = c->u_ghost;
    a.gh_ustride = c->gh_ustride;
    a.gh_mstride = c->gh_mstride;
@@ -183,11 +197,7 @@ int launch_ho(rmh_ctx *c, const double *u, double *du, double *m, double t)
    a.tab = c->d_tab;
    a.subvel = c->d_subvel;
    a.subx0 = c->d_subx0;
-   a.fgeo = nullptr;
-   a.face_rows = nullptr;
    a.subvmid = c->d_subvmid;
-   a.du = du;
-   a.m = m;
    a.xe_min = c->d_xe_min;
    a.xe_max = c->d_xe_max;
    a.cg_iters = c->d_cg;
@@ -195,9 +205,7 @@ int launch_ho(rmh_ctx *c, const double *u, double *du, double *m, double t)
    a.e_begin = 0;
    a.e_end = c->ne;
    a.bounds_type = 0;
-   a.dt_est = nullptr;
-   a.rd_subcell = c->lo_type == 3 ? 0 : 1;
-   a.t = t;
+   a.rd_subcell = rd_subcell_of(c);
    a.move = c->exec_mode == 1;
    a.alpha = c->exec_mode == 1 ? 1.0 : -1.0;
    a.upw = c->exec_mode == 1 ? 1.0 : -1.0;
@@ -209,88 +217,56 @@ int launch_ho(rmh_ctx *c, const double *u, double *du, double *m, double t)
    a.stencil27 = c->d_st27;
    a.gh_min = c->gh_min;
    a.gh_max = c->gh_max;
-   a.dt = 0.0;
-   a.x_base = nullptr;
-   a.rk_a = 0.0;
    a.rk_b = 1.0;
-   a.dt_rk = 0.0;
-   a.y_out = nullptr;
-   a.xe_min_out = nullptr;
-   a.xe_max_out = nullptr;
-   if (MODE == 2)
-   {
-      constexpr int P2 = P >= 2 ? P : 2; // subcell schemes need order >= 2 (checked by the callers)
-      constexpr int NB = K2Cfg<P2, true>::NB;
-      // (the face speed table is made the first time a kernel that reads it is launched)
-      {
-         if (int rc = ensure_face_table<P2>(c)) { return rc; }
-         a.fgeo = c->d_fgeo;
-         a.face_rows = c->d_face_rows;
-      }
-      a.xcd_chunk = xcd_chunk_for(c, (c->ne + NB - 1) / NB, NB, &a.xcd_weave);
-      a.xcd_rounds = a.xcd_chunk > 0 ? (((c->ne + NB - 1) / NB) >> 3) / a.xcd_chunk : 0;
-      a.xcd_inv = a.xcd_chunk > 1 ? (unsigned)(0x100000000ull / (unsigned)a.xcd_chunk) : 0xffffffffu;
-      a.reverse = 0;
-      hipLaunchKernelGGL((ho_kernel2<P2, 2>), dim3((c->ne + NB - 1) / NB), dim3(K2Cfg<P2, true>::NT), 0, c->stream, a);
-   }
-   else
-   {
-      constexpr int NB = K2Cfg<P>::NB;
-      // (the face speed table is made the first time a kernel that reads it is launched)
-      {
-         if (int rc = ensure_face_table<P>(c)) { return rc; }
-         a.fgeo = c->d_fgeo;
-         a.face_rows = c->d_face_rows;
-      }
-      a.xcd_chunk = xcd_chunk_for(c, (c->ne + NB - 1) / NB, NB, &a.xcd_weave);
-      a.xcd_rounds = a.xcd_chunk > 0 ? (((c->ne + NB - 1) / NB) >> 3) / a.xcd_chunk : 0;
-      a.xcd_inv = a.xcd_chunk > 1 ? (unsigned)(0x100000000ull / (unsigned)a.xcd_chunk) : 0xffffffffu;
-      a.reverse = 0;
-      hipLaunchKernelGGL((ho_kernel2<P, 0>), dim3((c->ne + NB - 1) / NB), dim3(K2Cfg<P>::NT), 0, c->stream, a);
-   }
+   return a; // (dt_est, x_base, y_out, xe_*_out null; rk_a, dt, dt_rk, reverse 0)
+}
+
+// one ho_kernel2<P, MODE> launch over the elements [a.e_begin, a.e_end): one workgroup per batch of NB elements (the kernel maps
+// blockIdx.x to a batch XCD-aware)
+template <int P, int MODE>
+int launch_ho2(rmh_ctx *c, HoArgs &a)
+{
+   using C = K2For<P, MODE>; // (the class the kernel takes its launch bounds and its batch from)
+   static_assert(C::NB == K2Cfg<P, (MODE >= 2), (MODE == 3)>::NB && C::NT == K2Cfg<P, (MODE >= 2), (MODE == 3)>::NT,
+                 "the u slot of the work region (K2Cfg NOU) must not change the shape of the launch");
+   // (the face speed table is made the first time a kernel that reads it is launched)
+   if (int rc = ensure_face_table<P>(c)) { return rc; }
+   a.fgeo = c->d_fgeo;
+   a.face_rows = c->d_face_rows;
+   const int nblk = (a.e_end - a.e_begin + C::NB - 1) / C::NB;
+   a.xcd_chunk = xcd_chunk_for(c, nblk, C::NB, &a.xcd_weave);
+   a.xcd_rounds = a.xcd_chunk > 0 ? (nblk >> 3) / a.xcd_chunk : 0;
+   a.xcd_inv = a.xcd_chunk > 1 ? (unsigned)(0x100000000ull / (unsigned)a.xcd_chunk) : 0xffffffffu;
+   hipLaunchKernelGGL((ho_kernel2<P, MODE>), dim3(nblk), dim3(C::NT), 0, c->stream, a);
    RMH_HIP(hipGetLastError());
    return 0;
+}
+
+// MODE 0: HO solver; MODE 2: RD solver alone (rd_subcell: see rd_subcell_of)
+template <int P, int MODE>
+int launch_ho(rmh_ctx *c, const double *u, double *du, double *m, double t, int rd_subcell)
+{
+   HoArgs a = ho_args(c);
+   a.u = u;
+   a.du = du;
+   a.m = m;
+   a.t = t;
+   a.rd_subcell = rd_subcell;
+   constexpr int PK = (MODE == 2 && P < 2) ? 2 : P; // subcell schemes need order >= 2 (checked by the callers)
+   return launch_ho2<PK, MODE>(c, a);
 }
 
 template <int P>
 int launch_stage_fused(rmh_ctx *c, const double *u, double dt, const double *x_base, double ra, double rb, double dt_rk,
                        double *y_out, double *du, int e_begin, int e_end)
 {
-   HoArgs a;
+   HoArgs a = ho_args(c);
    a.u = u;
-   a.u_ghost = c->u_ghost;
-   a.gh_ustride = c->gh_ustride;
-   a.gh_mstride = c->gh_mstride;
-   a.gh_compact = c->gh_compact;
-   a.x0 = c->d_x0h; // (ho_kernel2 takes the nodes in hierarchical form, see RMH_HIER in rmh_ho2.hpp)
-   a.vel = c->d_velh;
-   a.face_nbr = c->d_nbr;
-   a.tab = c->d_tab;
-   a.subvel = c->d_subvel;
-   a.subx0 = c->d_subx0;
-   a.fgeo = nullptr;
-   a.face_rows = nullptr;
-   a.subvmid = c->d_subvmid;
    a.du = du;
    a.m = c->d_m;
-   a.xe_min = c->d_xe_min;
-   a.xe_max = c->d_xe_max;
-   a.cg_iters = c->d_cg;
-   a.ne_owned = c->ne;
    a.e_begin = e_begin;
    a.e_end = e_end;
    a.t = c->t;
-   a.move = c->exec_mode == 1;
-   a.alpha = c->exec_mode == 1 ? 1.0 : -1.0;
-   a.upw = c->exec_mode == 1 ? 1.0 : -1.0;
-   a.rel2 = c->rel_tol * c->rel_tol;
-   a.abs2 = c->abs_tol * c->abs_tol;
-   a.max_iter = c->max_iter;
-   a.mass_fix = c->mass_fix;
-   a.jacobi_step = c->jacobi_step;
-   a.stencil27 = c->d_st27;
-   a.gh_min = c->gh_min;
-   a.gh_max = c->gh_max;
    a.dt = dt;
    a.x_base = x_base;
    a.rk_a = ra;
@@ -301,58 +277,35 @@ int launch_stage_fused(rmh_ctx *c, const double *u, double dt, const double *x_b
    a.xe_max_out = c->d_xe_max2;
    a.bounds_type = c->bounds_type;
    a.dt_est = c->dt_control ? c->d_dt_est : nullptr;
-   a.rd_subcell = c->lo_type == 3 ? 0 : 1;
-   // one workgroup per batch of NB elements (the kernel maps blockIdx.x to a batch XCD-aware)
+   a.reverse = c->alt_order ? (int)(c->xe_counter & 1) : 0;
    if (c->lo_type == 4 || c->lo_type == 3)
    {
       constexpr int P4 = P >= 2 ? P : 2; // subcell schemes need order >= 2 (checked by the caller)
-      using C = K2Cfg<P4, true, true>;
-      const int nblk = (e_end - e_begin + C::NB - 1) / C::NB;
-      const int grid = nblk;
-      a.xcd_chunk = xcd_chunk_for(c, nblk, C::NB, &a.xcd_weave);
-      a.xcd_rounds = a.xcd_chunk > 0 ? ((nblk) >> 3) / a.xcd_chunk : 0;
-      a.xcd_inv = a.xcd_chunk > 1 ? (unsigned)(0x100000000ull / (unsigned)a.xcd_chunk) : 0xffffffffu;
-      a.reverse = c->alt_order ? (int)(c->xe_counter & 1) : 0;
-      // (the face speed table is made the first time a kernel that reads it is launched)
-      {
-         if (int rc = ensure_face_table<P4>(c)) { return rc; }
-         a.fgeo = c->d_fgeo;
-         a.face_rows = c->d_face_rows;
-      }
-      hipLaunchKernelGGL((ho_kernel2<P4, 3>), dim3(grid), dim3(C::NT), 0, c->stream, a);
+      return launch_ho2<P4, 3>(c, a);
    }
-   else
-   {
-      using C = K2Cfg<P>;
-      const int nblk = (e_end - e_begin + C::NB - 1) / C::NB;
-      const int grid = nblk;
-      a.xcd_chunk = xcd_chunk_for(c, nblk, C::NB, &a.xcd_weave);
-      a.xcd_rounds = a.xcd_chunk > 0 ? ((nblk) >> 3) / a.xcd_chunk : 0;
-      a.xcd_inv = a.xcd_chunk > 1 ? (unsigned)(0x100000000ull / (unsigned)a.xcd_chunk) : 0xffffffffu;
-      a.reverse = c->alt_order ? (int)(c->xe_counter & 1) : 0;
-      // (the face speed table is made the first time a kernel that reads it is launched)
-      {
-         if (int rc = ensure_face_table<P>(c)) { return rc; }
-         a.fgeo = c->d_fgeo;
-         a.face_rows = c->d_face_rows;
-      }
-      hipLaunchKernelGGL((ho_kernel2<P, 1>), dim3(grid), dim3(C::NT), 0, c->stream, a);
-   }
-   RMH_HIP(hipGetLastError());
-   return 0;
+   return launch_ho2<P, 1>(c, a);
 }
 
-#define RMH_DISPATCH(c, expr)                                                                  \
+// (variadic: the statement may hold commas outside parentheses once a launch macro inside it is expanded.  The refusal of an
+// unknown order is a return: inside a lambda it leaves the lambda only, and the caller has to pass the code on)
+#define RMH_DISPATCH(c, ...)                                                                   \
    switch ((c)->p)                                                                             \
    {                                                                                           \
-      case 1: { constexpr int P = 1; expr; break; }                                            \
-      case 2: { constexpr int P = 2; expr; break; }                                            \
-      case 3: { constexpr int P = 3; expr; break; }                                            \
-      case 4: { constexpr int P = 4; expr; break; }                                            \
-      case 5: { constexpr int P = 5; expr; break; }                                            \
-      case 6: { constexpr int P = 6; expr; break; }                                            \
+      case 1: { constexpr int P = 1; __VA_ARGS__; break; }                                     \
+      case 2: { constexpr int P = 2; __VA_ARGS__; break; }                                     \
+      case 3: { constexpr int P = 3; __VA_ARGS__; break; }                                     \
+      case 4: { constexpr int P = 4; __VA_ARGS__; break; }                                     \
+      case 5: { constexpr int P = 5; __VA_ARGS__; break; }                                     \
+      case 6: { constexpr int P = 6; __VA_ARGS__; break; }                                     \
       default: return fail(RMH_ERR_INVALID, "unsupported order");                              \
    }
+
+// the same with constexpr int DIM = the context's dimension beside P
+#define RMH_DISPATCH_PD(c, ...)                                                                \
+   do {                                                                                        \
+      if ((c)->dim == 2) { constexpr int DIM = 2; RMH_DISPATCH(c, __VA_ARGS__); }              \
+      else { constexpr int DIM = 3; RMH_DISPATCH(c, __VA_ARGS__); }                            \
+   } while (0)
 
 // entry points that exist for hexahedra only
 #define RMH_3D_ONLY(c, name)                                                                                              \
@@ -392,7 +345,7 @@ int create_device_state_2d(rmh_ctx *c, const rmh_layout *L)
 }
 
 template <int P, int MODE>
-int launch_ho_2d(rmh_ctx *c, const double *u, double *du, double *m, double t)
+int launch_ho_2d(rmh_ctx *c, const double *u, double *du, double *m, double t, int rd_subcell)
 {
    Ho2Args a;
    a.u = u;
@@ -415,7 +368,7 @@ int launch_ho_2d(rmh_ctx *c, const double *u, double *du, double *m, double t)
    a.jacobi_step = c->jacobi_step;
    a.mass_fix = c->mass_fix;
    a.subvel = c->d_subvel;
-   a.rd_subcell = c->lo_type == 3 ? 0 : 1;
+   a.rd_subcell = rd_subcell;
    hipLaunchKernelGGL((ho2d_kernel<P, MODE>), dim3(c->ne), dim3(64), 0, c->stream, a);
    RMH_HIP(hipGetLastError());
    return 0;
@@ -518,6 +471,73 @@ int create_device_state(rmh_ctx *c, const rmh_layout *L)
    return 0;
 }
 
+// geometry, neighbours and ghost traces as the element-matrix kernels take them (rmh_upwind.hpp); dim = 2 keeps nodal nodes
+UpwArgs upwind_args(const rmh_ctx *c)
+{
+   UpwArgs a;
+   a.x0 = c->dim == 2 ? c->d_x0 : c->d_x0h;
+   a.vel = c->dim == 2 ? c->d_vel : c->d_velh;
+   a.tab = c->d_tab;
+   a.t = c->t;
+   a.move = c->exec_mode == 1 ? 1 : 0;
+   a.hier = c->dim == 2 ? 0 : (int)RMH_HIER;
+   a.alpha = c->exec_mode == 1 ? 1.0 : -1.0; // remhos.cpp:648-657
+   a.face_nbr = c->d_nbr;
+   a.ne_owned = c->ne;
+   a.u_ghost = c->u_ghost;
+   a.gh_ustride = c->gh_ustride;
+   a.gh_compact = c->gh_compact;
+   return a;
+}
+
+// (static LDS: 67 KB at s = 64, rmh_pdu.hpp -- gfx950 launches static allocations up to its 160 KiB per CU)
+template <int P, int DIM>
+void launch_lo_upwind_prec(rmh_ctx *c, const UpwArgs &a, const double *u, double *du_lo)
+{
+   hipLaunchKernelGGL((lo_upwind_prec_kernel<P, DIM>), dim3(c->ne), dim3(EfpCfg<P, DIM>::NT), 0, c->stream, a, u,
+                      (const double *)c->d_m, du_lo);
+}
+
+// first pass (20 updates, the elements' residual norms), the global norms and the stopping check K, second pass (K - 1 updates)
+template <int P, int DIM>
+void launch_neumann_iter(rmh_ctx *c, double *du)
+{
+   hipLaunchKernelGGL((neumann_iter_kernel<P, DIM>), dim3(c->ne), dim3(EfpCfg<P, DIM>::NT), 0, c->stream,
+                      (const double *)c->d_tab, (const double *)c->d_nm_wdet, (const double *)c->d_nm_rhs, (const double *)c->d_m,
+                      (const int *)c->d_nm_ctl, c->d_nm_part, du);
+   hipLaunchKernelGGL(neumann_norms_kernel, dim3(1), dim3(NEUMANN_NORMS_NT), 0, c->stream, (const double *)c->d_nm_part, c->ne,
+                      c->d_nm_norms, c->d_nm_ctl);
+   hipLaunchKernelGGL((neumann_iter_kernel<P, DIM>), dim3(c->ne), dim3(EfpCfg<P, DIM>::NT), 0, c->stream,
+                      (const double *)c->d_tab, (const double *)c->d_nm_wdet, (const double *)c->d_nm_rhs, (const double *)c->d_m,
+                      (const int *)c->d_nm_ctl + 1, (double *)nullptr, du);
+}
+
+// the lumped mass of the context's geometry: rmh_ho_apply (or an RD / Neumann call) has left it there since the last rmh_setup,
+// otherwise it is formed here
+int ensure_lumped_mass(rmh_ctx *c) { return c->ho_done ? 0 : rmh_compute_lumped_mass(c, c->t, c->d_m); }
+
+// the granular limiters share one signature, and every pointer of it is required: 0, or the refusal
+int check_limiter_args(const rmh_ctx *c, const double *u, const double *m, const double *du_ho, const double *du_lo, const double *u_min,
+                 const double *u_max, const double *du)
+{
+   if (!c || !u || !m || !du_ho || !du_lo || !u_min || !u_max || !du) { return fail(RMH_ERR_INVALID, "null argument"); }
+   return 0;
+}
+
+// RD solver alone, lo 4 (rd_subcell) or lo 3: the LO solver chosen for rmh_stage_fused (rmh_set_lo_type) is not its business
+int lo_rd(rmh_ctx *c, const double *u, double *du_lo, int rd_subcell)
+{
+   RMH_ENTER(c);
+   extrema_dropped(c);
+   return timed(c, 2, [&]() -> int {
+      int rc = 0;
+      if (c->dim == 2) { RMH_DISPATCH(c, rc = (launch_ho_2d<P, 2>(c, u, du_lo, c->d_m, c->t, rd_subcell))); }
+      else { RMH_DISPATCH(c, rc = (launch_ho<P, 2>(c, u, du_lo, c->d_m, c->t, rd_subcell))); }
+      if (!rc) { c->ho_done = true; } // lumped mass and element extrema are current
+      return rc;
+   });
+}
+
 } // namespace
 
 #ifdef RMH_STAMPS
@@ -548,6 +568,14 @@ extern "C" int rmh_debug_stamps(unsigned long long *out, int reset)
 // are refused while an exchange of u is in flight only.
 static const char *ghosts_not_ready(const rmh_ctx *c, int e_begin); // (both defined behind rmh_comm.hpp, which has struct Exchange)
 static const char *ghosts_in_flight(const rmh_ctx *c);
+
+// the granular readers of the neighbour traces: the ghost values of u are set and no exchange of them is in flight
+static int ghost_u_ready(const rmh_ctx *c)
+{
+   if (c->ng > 0 && !c->u_ghost) { return fail(RMH_ERR_STATE, "ghost values of u not set"); }
+   if (const char *why = ghosts_in_flight(c)) { return fail(RMH_ERR_STATE, why); }
+   return 0;
+}
 
 extern "C" {
 
@@ -748,18 +776,16 @@ int rmh_ho_apply(rmh_ctx *c, const double *u, double *du)
 {
    if (!c || !u || !du) { return fail(RMH_ERR_INVALID, "null argument"); }
    RMH_ENTER(c);
-   if (c->ng > 0 && !c->u_ghost) { return fail(RMH_ERR_STATE, "ghost values of u not set"); }
-   if (const char *why = ghosts_in_flight(c)) { return fail(RMH_ERR_STATE, why); }
-   EventPair ep;
-   int rc = timer_begin(c, 0, ep);
-   if (rc) { return rc; }
-   if (c->dim == 2) { RMH_DISPATCH(c, rc = (launch_ho_2d<P, 0>(c, u, du, c->d_m, c->t))); }
-   else { RMH_DISPATCH(c, rc = (launch_ho<P, 0>(c, u, du, c->d_m, c->t))); }
-   if (rc) { return rc; }
-   rc = timer_end(c, 0, ep);
-   c->ho_done = true;
-   extrema_dropped(c);
-   return rc;
+   if (int rc = ghost_u_ready(c)) { return rc; }
+   return timed(c, 0, [&]() -> int {
+      int rc = 0;
+      if (c->dim == 2) { RMH_DISPATCH(c, rc = (launch_ho_2d<P, 0>(c, u, du, c->d_m, c->t, rd_subcell_of(c)))); }
+      else { RMH_DISPATCH(c, rc = (launch_ho<P, 0>(c, u, du, c->d_m, c->t, rd_subcell_of(c)))); }
+      if (rc) { return rc; }
+      c->ho_done = true; // (once the launch is made, whatever becomes of the stopwatch)
+      extrema_dropped(c);
+      return 0;
+   });
 }
 
 const double *rmh_lumped_mass(rmh_ctx *c) { return c ? c->d_m : nullptr; }
@@ -771,7 +797,7 @@ int rmh_compute_lumped_mass(rmh_ctx *c, double t, double *m)
    int rc = 0;
    if (c->dim == 2)
    {
-      RMH_DISPATCH(c, rc = (launch_ho_2d<P, 4>(c, nullptr, nullptr, m, t)));
+      RMH_DISPATCH(c, rc = (launch_ho_2d<P, 4>(c, nullptr, nullptr, m, t, rd_subcell_of(c))));
       return rc;
    }
    RMH_DISPATCH(c, hipLaunchKernelGGL((lumped_mass_kernel<P>), dim3(c->ne), dim3(KCfg<P>::NT), 0, c->stream,
@@ -787,42 +813,12 @@ int rmh_lo_massavg(rmh_ctx *c, const double *u, const double *du_ho, double dt, 
    RMH_ENTER(c);
    extrema_dropped(c);
    if (!c->ho_done) { return fail(RMH_ERR_STATE, "rmh_lo_massavg needs the lumped mass of rmh_ho_apply"); }
-   EventPair ep;
-   int rc = timer_begin(c, 2, ep);
-   if (rc) { return rc; }
-   if (c->dim == 2)
-   {
-      RMH_DISPATCH(c, hipLaunchKernelGGL((lo_massavg_kernel<P, 2>), dim3(c->ne), dim3(KCfg<P, 2>::NT), 0, c->stream, u,
-                                         du_ho, (const double *)c->d_m, dt, du_lo));
-   }
-   else
-   {
-      RMH_DISPATCH(c, hipLaunchKernelGGL((lo_massavg_kernel<P>), dim3(c->ne), dim3(KCfg<P>::NT), 0, c->stream, u,
-                                         du_ho, (const double *)c->d_m, dt, du_lo));
-   }
-   RMH_HIP(hipGetLastError());
-   return timer_end(c, 2, ep);
+   return timed(c, 2, [&]() -> int {
+      RMH_DISPATCH_PD(c, hipLaunchKernelGGL((lo_massavg_kernel<P, DIM>), dim3(c->ne), dim3(KCfg<P, DIM>::NT), 0, c->stream, u, du_ho,
+                                            (const double *)c->d_m, dt, du_lo));
+      return 0;
+   });
 }
-
-namespace
-{
-int lo_rd(rmh_ctx *c, const double *u, double *du_lo, int lo_type)
-{
-   RMH_ENTER(c);
-   extrema_dropped(c);
-   EventPair ep;
-   int rc = timer_begin(c, 2, ep);
-   if (rc) { return rc; }
-   const int keep = c->lo_type;
-   c->lo_type = lo_type;
-   if (c->dim == 2) { RMH_DISPATCH(c, rc = (launch_ho_2d<P, 2>(c, u, du_lo, c->d_m, c->t))); }
-   else { RMH_DISPATCH(c, rc = (launch_ho<P, 2>(c, u, du_lo, c->d_m, c->t))); }
-   c->lo_type = keep;
-   if (rc) { return rc; }
-   c->ho_done = true; // lumped mass and element extrema are current
-   return timer_end(c, 2, ep);
-}
-} // namespace
 
 int rmh_lo_rdsubcell(rmh_ctx *c, const double *u, double *du_lo)
 {
@@ -830,7 +826,7 @@ int rmh_lo_rdsubcell(rmh_ctx *c, const double *u, double *du_lo)
    if (c->p < 2) { return fail(RMH_ERR_INVALID, "Subcell schemes require FE order > 2."); } // remhos.cpp:612-616
    if (!c->d_subvel) { return fail(RMH_ERR_STATE, "rmh_lo_rdsubcell needs rmh_layout.subcell_vel"); }
    if (c->ng > 0 && !c->u_ghost) { return fail(RMH_ERR_STATE, "ghost values of u not set"); }
-   return lo_rd(c, u, du_lo, 4);
+   return lo_rd(c, u, du_lo, 1);
 }
 
 int rmh_lo_rd(rmh_ctx *c, const double *u, double *du_lo)
@@ -838,23 +834,15 @@ int rmh_lo_rd(rmh_ctx *c, const double *u, double *du_lo)
    if (!c || !u || !du_lo) { return fail(RMH_ERR_INVALID, "null argument"); }
    if (c->p < 2) { return fail(RMH_ERR_INVALID, "rmh_lo_rd: the RD kernel is built for orders >= 2"); }
    if (c->ng > 0 && !c->u_ghost) { return fail(RMH_ERR_STATE, "ghost values of u not set"); }
-   return lo_rd(c, u, du_lo, 3);
+   return lo_rd(c, u, du_lo, 0);
 }
 
 int rmh_elem_minmax(rmh_ctx *c, const double *u, double *xe_min, double *xe_max)
 {
    if (!c || !u || !xe_min || !xe_max) { return fail(RMH_ERR_INVALID, "null argument"); }
    RMH_ENTER(c);
-   if (c->dim == 2)
-   {
-      RMH_DISPATCH(c, hipLaunchKernelGGL((elem_minmax_kernel<P, 2>), dim3(SCfg<P, 2>::grid(c->ne, SCfg<P, 2>::U8)),
-                                         dim3(SCfg<P, 2>::NT), 0, c->stream, u, xe_min, xe_max, c->ne));
-   }
-   else
-   {
-      RMH_DISPATCH(c, hipLaunchKernelGGL((elem_minmax_kernel<P>), dim3(SCfg<P>::grid(c->ne, SCfg<P>::U8)), dim3(SCfg<P>::NT), 0,
-                                         c->stream, u, xe_min, xe_max, c->ne));
-   }
+   RMH_DISPATCH_PD(c, hipLaunchKernelGGL((elem_minmax_kernel<P, DIM>), dim3(SCfg<P, DIM>::grid(c->ne, SCfg<P, DIM>::U8)),
+                                         dim3(SCfg<P, DIM>::NT), 0, c->stream, u, xe_min, xe_max, c->ne));
    RMH_HIP(hipGetLastError());
    return RMH_OK;
 }
@@ -867,18 +855,9 @@ int rmh_bounds(rmh_ctx *c, const double *xe_min, const double *xe_max, double *u
    if (c->ng > 0 && (!c->gh_min || !c->gh_max)) { return fail(RMH_ERR_STATE, "ghost extrema not set"); }
    if (const char *why = ghosts_in_flight(c)) { return fail(RMH_ERR_STATE, why); }
    const int wide = (((uintptr_t)u_min | (uintptr_t)u_max) & 15) == 0; // 16-byte stores
-   if (c->dim == 2)
-   {
-      RMH_DISPATCH(c, hipLaunchKernelGGL((bounds_kernel<P, 2>), dim3(SCfg<P, 2>::grid(c->ne, SCfg<P, 2>::UB)), dim3(SCfg<P, 2>::NT), 0, c->stream,
-                                         c->bounds_type, (const int *)c->d_st27, c->ne, xe_min, xe_max, c->gh_min, c->gh_max, c->gh_mstride, u_min,
-                                         u_max, wide));
-   }
-   else
-   {
-      RMH_DISPATCH(c, hipLaunchKernelGGL((bounds_kernel<P>), dim3(SCfg<P>::grid(c->ne, SCfg<P>::UB)), dim3(SCfg<P>::NT), 0, c->stream,
-                                         c->bounds_type, (const int *)c->d_st27, c->ne, xe_min, xe_max, c->gh_min, c->gh_max, c->gh_mstride, u_min,
-                                         u_max, wide));
-   }
+   RMH_DISPATCH_PD(c, hipLaunchKernelGGL((bounds_kernel<P, DIM>), dim3(SCfg<P, DIM>::grid(c->ne, SCfg<P, DIM>::UB)), dim3(SCfg<P, DIM>::NT), 0,
+                                         c->stream, c->bounds_type, (const int *)c->d_st27, c->ne, xe_min, xe_max, c->gh_min, c->gh_max,
+                                         c->gh_mstride, u_min, u_max, wide));
    RMH_HIP(hipGetLastError());
    return RMH_OK;
 }
@@ -886,122 +865,46 @@ int rmh_bounds(rmh_ctx *c, const double *xe_min, const double *xe_max, double *u
 int rmh_fct_clipscale(rmh_ctx *c, const double *u, const double *m, const double *du_ho, const double *du_lo,
                       const double *u_min, const double *u_max, double dt, double *du)
 {
-   if (!c || !u || !m || !du_ho || !du_lo || !u_min || !u_max || !du)
-   {
-      return fail(RMH_ERR_INVALID, "null argument");
-   }
+   if (int rc = check_limiter_args(c, u, m, du_ho, du_lo, u_min, u_max, du)) { return rc; }
    RMH_ENTER(c);
    extrema_dropped(c);
-   EventPair ep;
-   int rc = timer_begin(c, 3, ep);
-   if (rc) { return rc; }
-   if (c->dim == 2)
-   {
-      RMH_DISPATCH(c, hipLaunchKernelGGL((fct_clipscale_kernel<P, 2>), dim3(c->ne), dim3(KCfg<P, 2>::NT), 0, c->stream, u, m,
-                                         du_ho, du_lo, u_min, u_max, dt, du));
-   }
-   else
-   {
-      RMH_DISPATCH(c, hipLaunchKernelGGL((fct_clipscale_kernel<P>), dim3(c->ne), dim3(KCfg<P>::NT), 0, c->stream, u, m,
-                                         du_ho, du_lo, u_min, u_max, dt, du));
-   }
-   RMH_HIP(hipGetLastError());
-   return timer_end(c, 3, ep);
+   return timed(c, 3, [&]() -> int {
+      RMH_DISPATCH_PD(c, hipLaunchKernelGGL((fct_clipscale_kernel<P, DIM>), dim3(c->ne), dim3(KCfg<P, DIM>::NT), 0, c->stream, u, m, du_ho,
+                                            du_lo, u_min, u_max, dt, du));
+      return 0;
+   });
 }
 
 int rmh_fct_projection(rmh_ctx *c, const double *u, const double *m, const double *du_ho, const double *du_lo,
                        const double *u_min, const double *u_max, double dt, double *du)
 {
-   if (!c || !u || !m || !du_ho || !du_lo || !u_min || !u_max || !du)
-   {
-      return fail(RMH_ERR_INVALID, "null argument");
-   }
+   if (int rc = check_limiter_args(c, u, m, du_ho, du_lo, u_min, u_max, du)) { return rc; }
    if (!(dt > 0.0)) { return fail(RMH_ERR_INVALID, "dt must be positive"); }
    RMH_ENTER(c);
    extrema_dropped(c);
-   EventPair ep;
-   int rc = timer_begin(c, 3, ep);
-   if (rc) { return rc; }
-   const int move = c->exec_mode == 1 ? 1 : 0;
-   if (c->dim == 2)
-   {
-      RMH_DISPATCH(c, hipLaunchKernelGGL((fct_projection_kernel<P, 2>), dim3(c->ne), dim3(EfpCfg<P, 2>::NT), 0, c->stream,
-                                         (const double *)c->d_x0, (const double *)c->d_vel, (const double *)c->d_tab, c->t, move, 0,
-                                         u, du_ho, du_lo, u_min, u_max, dt, du));
-   }
-   else
-   {
-      RMH_DISPATCH(c, hipLaunchKernelGGL((fct_projection_kernel<P, 3>), dim3(c->ne), dim3(EfpCfg<P, 3>::NT), 0, c->stream,
-                                         (const double *)c->d_x0h, (const double *)c->d_velh, (const double *)c->d_tab, c->t, move,
-                                         (int)RMH_HIER, u, du_ho, du_lo, u_min, u_max, dt, du));
-   }
-   RMH_HIP(hipGetLastError());
-   return timer_end(c, 3, ep);
+   // (for its geometry -- nodes nodal at dim = 2, hierarchical at dim = 3; the neighbour and ghost fields are not used)
+   const UpwArgs g = upwind_args(c);
+   return timed(c, 3, [&]() -> int {
+      RMH_DISPATCH_PD(c, hipLaunchKernelGGL((fct_projection_kernel<P, DIM>), dim3(c->ne), dim3(EfpCfg<P, DIM>::NT), 0, c->stream, g.x0,
+                                            g.vel, g.tab, g.t, g.move, g.hier, u, du_ho, du_lo, u_min, u_max, dt, du));
+      return 0;
+   });
 }
-
-namespace
-{
-UpwArgs upwind_args(const rmh_ctx *c)
-{
-   UpwArgs a;
-   a.x0 = c->dim == 2 ? c->d_x0 : c->d_x0h;
-   a.vel = c->dim == 2 ? c->d_vel : c->d_velh;
-   a.tab = c->d_tab;
-   a.t = c->t;
-   a.move = c->exec_mode == 1 ? 1 : 0;
-   a.hier = c->dim == 2 ? 0 : (int)RMH_HIER;
-   a.alpha = c->exec_mode == 1 ? 1.0 : -1.0; // remhos.cpp:648-657
-   a.face_nbr = c->d_nbr;
-   a.ne_owned = c->ne;
-   a.u_ghost = c->u_ghost;
-   a.gh_ustride = c->gh_ustride;
-   a.gh_compact = c->gh_compact;
-   return a;
-}
-} // namespace
 
 int rmh_lo_upwind(rmh_ctx *c, const double *u, double *du_lo)
 {
    if (!c || !u || !du_lo) { return fail(RMH_ERR_INVALID, "null argument"); }
-   if (c->ng > 0 && !c->u_ghost) { return fail(RMH_ERR_STATE, "ghost values of u not set"); }
-   if (const char *why = ghosts_in_flight(c)) { return fail(RMH_ERR_STATE, why); }
+   if (int rc = ghost_u_ready(c)) { return rc; }
    RMH_ENTER(c);
    extrema_dropped(c);
-   // the lumped mass of this geometry: rmh_ho_apply has just left it in the context, otherwise it is formed here
-   if (!c->ho_done)
-   {
-      const int rc = rmh_compute_lumped_mass(c, c->t, c->d_m);
-      if (rc) { return rc; }
-   }
-   EventPair ep;
-   int rc = timer_begin(c, 2, ep);
-   if (rc) { return rc; }
+   if (int rc = ensure_lumped_mass(c)) { return rc; }
    const UpwArgs a = upwind_args(c);
-   if (c->dim == 2)
-   {
-      RMH_DISPATCH(c, hipLaunchKernelGGL((lo_upwind_kernel<P, 2>), dim3(c->ne), dim3(EfpCfg<P, 2>::NT), 0, c->stream, a, u,
-                                         (const double *)c->d_m, du_lo));
-   }
-   else
-   {
-      RMH_DISPATCH(c, hipLaunchKernelGGL((lo_upwind_kernel<P, 3>), dim3(c->ne), dim3(EfpCfg<P, 3>::NT), 0, c->stream, a, u,
-                                         (const double *)c->d_m, du_lo));
-   }
-   RMH_HIP(hipGetLastError());
-   return timer_end(c, 2, ep);
+   return timed(c, 2, [&]() -> int {
+      RMH_DISPATCH_PD(c, hipLaunchKernelGGL((lo_upwind_kernel<P, DIM>), dim3(c->ne), dim3(EfpCfg<P, DIM>::NT), 0, c->stream, a, u,
+                                            (const double *)c->d_m, du_lo));
+      return 0;
+   });
 }
-
-namespace
-{
-// (static LDS: 67 KB at s = 64, rmh_pdu.hpp -- gfx950 launches static allocations up to its 160 KiB per CU)
-extern "C++" template <int P, int DIM>
-int launch_lo_upwind_prec(rmh_ctx *c, const UpwArgs &a, const double *u, double *du_lo)
-{
-   hipLaunchKernelGGL((lo_upwind_prec_kernel<P, DIM>), dim3(c->ne), dim3(EfpCfg<P, DIM>::NT), 0, c->stream, a, u,
-                      (const double *)c->d_m, du_lo);
-   return RMH_OK;
-}
-} // namespace
 
 int rmh_lo_upwind_prec(rmh_ctx *c, const double *u, double *du_lo)
 {
@@ -1011,61 +914,26 @@ int rmh_lo_upwind_prec(rmh_ctx *c, const double *u, double *du_lo)
       return fail(RMH_ERR_INVALID, "rmh_lo_upwind_prec (-lo 2): order " + std::to_string(c->p) +
                                       " in 3-D is not supported: the element's dense matrices must fit the LDS (orders 1 to 3 in 3-D, 1 to 6 in 2-D)");
    }
-   if (c->ng > 0 && !c->u_ghost) { return fail(RMH_ERR_STATE, "ghost values of u not set"); }
-   if (const char *why = ghosts_in_flight(c)) { return fail(RMH_ERR_STATE, why); }
+   if (int rc = ghost_u_ready(c)) { return rc; }
    RMH_ENTER(c);
    extrema_dropped(c);
-   // the lumped mass of this geometry: rmh_ho_apply has just left it in the context, otherwise it is formed here
-   if (!c->ho_done)
-   {
-      const int rc = rmh_compute_lumped_mass(c, c->t, c->d_m);
-      if (rc) { return rc; }
-   }
-   EventPair ep;
-   int rc = timer_begin(c, 2, ep);
-   if (rc) { return rc; }
+   if (int rc = ensure_lumped_mass(c)) { return rc; }
    const UpwArgs a = upwind_args(c);
-   if (c->dim == 2)
-   {
-      RMH_DISPATCH(c, (rc = launch_lo_upwind_prec<P, 2>(c, a, u, du_lo)));
-   }
-   else
-   {
-      switch (c->p)
+   return timed(c, 2, [&]() -> int {
+      if (c->dim == 2) { RMH_DISPATCH(c, (launch_lo_upwind_prec<P, 2>(c, a, u, du_lo))); }
+      else
       {
-         case 1: rc = launch_lo_upwind_prec<1, 3>(c, a, u, du_lo); break;
-         case 2: rc = launch_lo_upwind_prec<2, 3>(c, a, u, du_lo); break;
-         case 3: rc = launch_lo_upwind_prec<3, 3>(c, a, u, du_lo); break;
-         default: return fail(RMH_ERR_INVALID, "unsupported order");
+         switch (c->p) // (the static LDS of the orders 4 to 6 does not fit: those kernels must not be instantiated)
+         {
+            case 1: launch_lo_upwind_prec<1, 3>(c, a, u, du_lo); break;
+            case 2: launch_lo_upwind_prec<2, 3>(c, a, u, du_lo); break;
+            case 3: launch_lo_upwind_prec<3, 3>(c, a, u, du_lo); break;
+            default: return fail(RMH_ERR_INVALID, "unsupported order");
+         }
       }
-   }
-   if (rc) { return rc; }
-   RMH_HIP(hipGetLastError());
-   return timer_end(c, 2, ep);
+      return 0;
+   });
 }
-
-namespace
-{
-extern "C++" template <int P, int DIM>
-void launch_neumann_rhs(rmh_ctx *c, const UpwArgs &a, const double *u)
-{
-   hipLaunchKernelGGL((neumann_rhs_kernel<P, DIM>), dim3(c->ne), dim3(EfpCfg<P, DIM>::NT), 0, c->stream, a, u, c->d_nm_rhs, c->d_nm_wdet);
-}
-
-// first pass (20 updates, the elements' residual norms), the global norms and the stopping check K, second pass (K - 1 updates)
-extern "C++" template <int P, int DIM>
-void launch_neumann_iter(rmh_ctx *c, double *du)
-{
-   hipLaunchKernelGGL((neumann_iter_kernel<P, DIM>), dim3(c->ne), dim3(EfpCfg<P, DIM>::NT), 0, c->stream,
-                      (const double *)c->d_tab, (const double *)c->d_nm_wdet, (const double *)c->d_nm_rhs, (const double *)c->d_m,
-                      (const int *)c->d_nm_ctl, c->d_nm_part, du);
-   hipLaunchKernelGGL(neumann_norms_kernel, dim3(1), dim3(NEUMANN_NORMS_NT), 0, c->stream, (const double *)c->d_nm_part, c->ne,
-                      c->d_nm_norms, c->d_nm_ctl);
-   hipLaunchKernelGGL((neumann_iter_kernel<P, DIM>), dim3(c->ne), dim3(EfpCfg<P, DIM>::NT), 0, c->stream,
-                      (const double *)c->d_tab, (const double *)c->d_nm_wdet, (const double *)c->d_nm_rhs, (const double *)c->d_m,
-                      (const int *)c->d_nm_ctl + 1, (double *)nullptr, du);
-}
-} // namespace
 
 int rmh_ho_neumann(rmh_ctx *c, const double *u, double *du)
 {
@@ -1088,35 +956,23 @@ int rmh_ho_neumann(rmh_ctx *c, const double *u, double *du)
       c->d_nm_ctl = ctl;
       RMH_HIP(hipMemcpy(ctl, ctl0, sizeof(ctl0), hipMemcpyHostToDevice));
    }
-   // the lumped mass of this geometry: formed here unless an HO / RD call has left it since the last rmh_setup; the element
-   // extrema of u go with it (what ho_done promises to rmh_limit_fused)
-   if (!c->ho_done)
-   {
-      const int rc = rmh_compute_lumped_mass(c, c->t, c->d_m);
-      if (rc) { return rc; }
-   }
-   {
-      const int rc = rmh_elem_minmax(c, u, c->d_xe_min, c->d_xe_max);
-      if (rc) { return rc; }
-   }
+   // the lumped mass of this geometry; the element extrema of u go with it (what ho_done promises to rmh_limit_fused)
+   if (int rc = ensure_lumped_mass(c)) { return rc; }
+   if (int rc = rmh_elem_minmax(c, u, c->d_xe_min, c->d_xe_max)) { return rc; }
    const UpwArgs a = upwind_args(c);
-   EventPair ep;
-   int rc = timer_begin(c, 0, ep);
+   const int rc = timed(c, 0, [&]() -> int {
+      RMH_DISPATCH_PD(c, hipLaunchKernelGGL((neumann_rhs_kernel<P, DIM>), dim3(c->ne), dim3(EfpCfg<P, DIM>::NT), 0, c->stream, a, u,
+                                            c->d_nm_rhs, c->d_nm_wdet));
+      return 0;
+   });
    if (rc) { return rc; }
-   if (c->dim == 2) { RMH_DISPATCH(c, (launch_neumann_rhs<P, 2>(c, a, u))); }
-   else { RMH_DISPATCH(c, (launch_neumann_rhs<P, 3>(c, a, u))); }
-   RMH_HIP(hipGetLastError());
-   rc = timer_end(c, 0, ep);
-   if (rc) { return rc; }
-   rc = timer_begin(c, 1, ep);
-   if (rc) { return rc; }
-   if (c->dim == 2) { RMH_DISPATCH(c, (launch_neumann_iter<P, 2>(c, du))); }
-   else { RMH_DISPATCH(c, (launch_neumann_iter<P, 3>(c, du))); }
-   RMH_HIP(hipGetLastError());
-   rc = timer_end(c, 1, ep);
-   c->ho_done = true;
-   extrema_dropped(c);
-   return rc;
+   return timed(c, 1, [&]() -> int {
+      RMH_DISPATCH_PD(c, (launch_neumann_iter<P, DIM>(c, du)));
+      RMH_HIP(hipGetLastError());
+      c->ho_done = true; // (once the launches are made, whatever becomes of the stopwatch)
+      extrema_dropped(c);
+      return 0;
+   });
 }
 
 int rmh_last_neumann(rmh_ctx *c, int *updates, double norms[20])
@@ -1136,10 +992,7 @@ int rmh_last_neumann(rmh_ctx *c, int *updates, double norms[20])
 int rmh_fct_fluxbased(rmh_ctx *c, const double *u, const double *m, const double *du_ho, const double *du_lo,
                       const double *u_min, const double *u_max, double dt, double *du)
 {
-   if (!c || !u || !m || !du_ho || !du_lo || !u_min || !u_max || !du)
-   {
-      return fail(RMH_ERR_INVALID, "null argument");
-   }
+   if (int rc = check_limiter_args(c, u, m, du_ho, du_lo, u_min, u_max, du)) { return rc; }
    if (!(dt > 0.0)) { return fail(RMH_ERR_INVALID, "dt must be positive"); }
    if (c->ng > 0)
    {
@@ -1147,22 +1000,12 @@ int rmh_fct_fluxbased(rmh_ctx *c, const double *u, const double *m, const double
    }
    RMH_ENTER(c);
    extrema_dropped(c);
-   EventPair ep;
-   int rc = timer_begin(c, 3, ep);
-   if (rc) { return rc; }
    const UpwArgs a = upwind_args(c);
-   if (c->dim == 2)
-   {
-      RMH_DISPATCH(c, hipLaunchKernelGGL((fct_fluxbased_kernel<P, 2>), dim3(c->ne), dim3(EfpCfg<P, 2>::NT), 0, c->stream, a, u, m,
-                                         du_ho, du_lo, u_min, u_max, dt, du));
-   }
-   else
-   {
-      RMH_DISPATCH(c, hipLaunchKernelGGL((fct_fluxbased_kernel<P, 3>), dim3(c->ne), dim3(EfpCfg<P, 3>::NT), 0, c->stream, a, u, m,
-                                         du_ho, du_lo, u_min, u_max, dt, du));
-   }
-   RMH_HIP(hipGetLastError());
-   return timer_end(c, 3, ep);
+   return timed(c, 3, [&]() -> int {
+      RMH_DISPATCH_PD(c, hipLaunchKernelGGL((fct_fluxbased_kernel<P, DIM>), dim3(c->ne), dim3(EfpCfg<P, DIM>::NT), 0, c->stream, a, u, m,
+                                            du_ho, du_lo, u_min, u_max, dt, du));
+      return 0;
+   });
 }
 
 int rmh_product_ratio(rmh_ctx *c, const double *us, const double *u, double *s, unsigned char *active_el,
@@ -1215,21 +1058,19 @@ int rmh_fct_product(rmh_ctx *c, const double *us, const double *m, const double 
    if (!(dt > 0.0)) { return fail(RMH_ERR_INVALID, "dt must be positive"); }
    RMH_ENTER(c);
    extrema_dropped(c);
-   EventPair ep;
-   int rc = timer_begin(c, 3, ep);
-   if (rc) { return rc; }
-   if (c->dim == 2)
-   {
-      RMH_DISPATCH(c, hipLaunchKernelGGL((fct_product2d_kernel<P>), dim3(P2Cfg<P>::grid(c->ne)), dim3(P2Cfg<P>::NT), 0, c->stream,
-                                         us, m, d_us_ho, s_min, s_max, u_new, active_el, active_dofs, dt, d_us, c->ne));
-   }
-   else
-   {
-      RMH_DISPATCH(c, hipLaunchKernelGGL((fct_product_kernel<P>), dim3(c->ne), dim3(KCfg<P>::NT), 0, c->stream, us, m, d_us_ho,
-                                         s_min, s_max, u_new, active_el, active_dofs, dt, d_us));
-   }
-   RMH_HIP(hipGetLastError());
-   return timer_end(c, 3, ep);
+   return timed(c, 3, [&]() -> int {
+      if (c->dim == 2)
+      {
+         RMH_DISPATCH(c, hipLaunchKernelGGL((fct_product2d_kernel<P>), dim3(P2Cfg<P>::grid(c->ne)), dim3(P2Cfg<P>::NT), 0, c->stream,
+                                            us, m, d_us_ho, s_min, s_max, u_new, active_el, active_dofs, dt, d_us, c->ne));
+      }
+      else
+      {
+         RMH_DISPATCH(c, hipLaunchKernelGGL((fct_product_kernel<P>), dim3(c->ne), dim3(KCfg<P>::NT), 0, c->stream, us, m, d_us_ho,
+                                            s_min, s_max, u_new, active_el, active_dofs, dt, d_us));
+      }
+      return 0;
+   });
 }
 
 
@@ -1263,13 +1104,11 @@ static int limit_fused_impl(rmh_ctx *c, const double *u, const double *du_ho, co
    la.b = b;
    la.dt_rk = dt_rk;
    la.y_out = y_out;
-   EventPair ep;
-   int rc = timer_begin(c, 3, ep);
-   if (rc) { return rc; }
-   if (c->dim == 2) {   RMH_DISPATCH(c, hipLaunchKernelGGL((limit_fused_kernel<P, 2>), dim3(SCfg<P, 2>::grid(c->ne, SCfg<P, 2>::U4)), dim3(SCfg<P, 2>::NT), 0, c->stream, la)); }
-   else {   RMH_DISPATCH(c, hipLaunchKernelGGL((limit_fused_kernel<P>), dim3(SCfg<P>::grid(c->ne, SCfg<P>::U4)), dim3(SCfg<P>::NT), 0, c->stream, la)); }
-   RMH_HIP(hipGetLastError());
-   return timer_end(c, 3, ep);
+   return timed(c, 3, [&]() -> int {
+      RMH_DISPATCH_PD(c, hipLaunchKernelGGL((limit_fused_kernel<P, DIM>), dim3(SCfg<P, DIM>::grid(c->ne, SCfg<P, DIM>::U4)),
+                                            dim3(SCfg<P, DIM>::NT), 0, c->stream, la));
+      return 0;
+   });
 }
 
 int rmh_limit_fused(rmh_ctx *c, const double *u, const double *du_ho, double dt, double *du, const double *x_base,
@@ -1344,10 +1183,10 @@ int rmh_stage_fused_chain(rmh_ctx *c, const double *u, double dt, const double *
    c->xe_token = 0; // (until this stage is finished, no token is valid)
    if (e_end > e_begin)
    {
-      EventPair ep;
-      rc = timer_begin(c, 0, ep);
-      if (!rc) { RMH_DISPATCH(c, rc = launch_stage_fused<P>(c, u, dt, x_base, a, b, dt_rk, y_out, du, e_begin, e_end)); }
-      if (!rc) { rc = timer_end(c, 0, ep); }
+      // (dispatched out here: a refused order returns from this function and leaves the stage open, as it always did)
+      decltype(&launch_stage_fused<1>) launch = nullptr;
+      RMH_DISPATCH(c, launch = launch_stage_fused<P>);
+      rc = timed(c, 0, [&]() -> int { return launch(c, u, dt, x_base, a, b, dt_rk, y_out, du, e_begin, e_end); });
       if (rc)
       {
          c->stage_open = false; // a failed stage leaves no extrema behind: the next one recomputes them

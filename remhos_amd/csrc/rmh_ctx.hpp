@@ -1,5 +1,5 @@
 // Private to the library: the context behind the opaque rmh_ctx of include/rmh.h, shared by the entry points
-// (rmh_api.hip) and the neighbour exchange (rmh_comm.hip).
+// (rmh_api.hip) and the neighbour exchange (rmh_comm.hpp, included by it).
 #pragma once
 #include "../../include/rmh.h"
 #include <hip/hip_runtime.h>
