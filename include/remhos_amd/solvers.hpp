@@ -332,6 +332,41 @@ public:
    void ComputeBounds(const Vector &el_min, const Vector &el_max, Vector &dof_min, Vector &dof_max) const;
 };
 
+// Monolithic solvers (remhos_mono.hpp:25-40): these solve the transport / remap problem directly, without splitting into HO / LO / FCT
+// phases; AdvectionOperator::Mult hands them the whole stage and LimitMult does nothing (remhos.cpp:1687).
+class MonolithicSolver
+{
+protected:
+   ParFiniteElementSpace &pfes;
+
+public:
+   MonolithicSolver(ParFiniteElementSpace &space) : pfes(space) {}
+   virtual ~MonolithicSolver() {}
+   virtual void CalcSolution(const Vector &u, Vector &du) const = 0;
+};
+
+// remhos_mono.hpp:45-66, remhos_mono.cpp:25-356 (-mono 1, MonolithicSolverType::ResDistMono): ComputeElementsMinMax + ComputeBounds of
+// u, then the element-local residual-distribution update with the mass iteration (rmh_mono_rd).  The assembled convection and mass
+// matrices, the lumped mass vector and the Assembly object of the reference's constructor have no counterpart: the kernel forms the
+// element's rows on the mesh of the operator's time and reads the context's lumped mass.  The velocity coefficient is replaced by
+// what the constructor makes of it, scale(e) on the initial mesh (HOST array [ne]: rmhd_case_mono_scale).  Built for
+// subcell = false and no smoothness indicator; anything else aborts.  One block.
+class MonoRDSolver : public MonolithicSolver
+{
+protected:
+   DofInfo &dofs;
+   SmoothnessIndicator *smth_indicator;
+   Vector scale;
+   bool subcell_scheme;
+   const bool time_dep;
+   const bool mass_lim;
+
+public:
+   MonoRDSolver(ParFiniteElementSpace &space, DofInfo &dofs_, SmoothnessIndicator *si, const double *scale_host, bool subcell,
+                bool timedep, bool masslim);
+   void CalcSolution(const Vector &u, Vector &du) const override;
+};
+
 // remhos_sync.hpp: active element / dof flags and the ratio s = us / u of product remap (device kernels)
 void ComputeBoolIndicators(ParFiniteElementSpace &pfes, const Vector &u, Array<bool> &ind_elem, Array<bool> &ind_dofs);
 void ComputeRatio(ParFiniteElementSpace &pfes, const Vector &us, const Vector &u, Vector &s, Array<bool> &bool_el,
@@ -391,6 +426,9 @@ public:
    // -vb (remhos.cpp:195, 1115): LimitMult checks the LO and the limited update against the dof bounds (:1824-1837).  With
    // the fused limiter the bounds and the LO rate are formed a second time by the granular kernels for the check.
    bool verify_bounds = false;
+   // -mono (remhos.cpp:997-1013, 1687): when set, Mult is rmh_setup + this solver's CalcSolution and LimitMult does nothing; the HO /
+   // LO / FCT solvers are not called
+   MonolithicSolver *mono_solver = nullptr;
 
    AdvectionOperator(ParFiniteElementSpace &space, DofInfo &dofs_, HOSolver *hos, LOSolver *los, FCTSolver *fct,
                      bool fused_limiter, bool product_sync = false);

@@ -78,7 +78,7 @@ typedef struct {
  * BASELINE configs[0]'s mesh family.  Layout: x0 / vel [ne][2][9] (node a = ax + 3*ay), face_nbr [ne][4] (f = 2*c + side),
  * `stencil27` = the 3 x 3 element stencil [ne][9] (entry (ox+1) + 3*(oy+1)), ne_ghost = 0, subcell_vel [ne][2][(p+1)^2] or NULL; E-vectors
  * carry (p+1)^2 doubles per element; Q = p + 2 quadrature points per direction.  Entry points: rmh_setup,
- * rmh_ho_apply, rmh_ho_neumann, rmh_last_neumann, rmh_lumped_mass, rmh_compute_lumped_mass, rmh_lo_massavg, rmh_lo_rd, rmh_lo_rdsubcell, rmh_lo_upwind, rmh_lo_upwind_prec, rmh_elem_minmax, rmh_bounds, rmh_fct_clipscale, rmh_fct_projection, rmh_fct_fluxbased,
+ * rmh_ho_apply, rmh_ho_neumann, rmh_last_neumann, rmh_lumped_mass, rmh_compute_lumped_mass, rmh_lo_massavg, rmh_lo_rd, rmh_lo_rdsubcell, rmh_lo_upwind, rmh_lo_upwind_prec, rmh_mono_rd, rmh_elem_minmax, rmh_bounds, rmh_fct_clipscale, rmh_fct_projection, rmh_fct_fluxbased,
  * rmh_product_ratio, rmh_elem_minmax_masked, rmh_fct_product (remhos_amd/csrc/rmh_product2d.hpp: a wavefront per element), rmh_check_violation,
  * rmh_limit_fused, rmh_limit_fused_lo, rmh_stage_fused (the whole rank: HO kernel, RD solver for lo 3 / 4 and the fused limiter run
  * as a sequence inside the library; no tokens), the mass-rule / bounds-type / dt-control setters and getters, timers.  Everything
@@ -313,6 +313,27 @@ int rmh_lo_upwind_prec(rmh_ctx *ctx, const double *u, double *du_lo);
 int rmh_fct_fluxbased(rmh_ctx *ctx, const double *u, const double *m,
                       const double *du_ho, const double *du_lo,
                       const double *u_min, const double *u_max, double dt, double *du);
+
+/* MonolithicSolver::CalcSolution, MonoRDSolver with subcell_scheme = false and no smoothness indicator (-mono 1; remhos_mono.hpp,
+ * remhos_mono.cpp:60-356, remhos.cpp:997-1013, 1687): du is the whole right-hand side of a stage -- the volume term K_vol u split by
+ * alpha(xi_min, xi_max, u), Assembly::NonlinFluxLumping on every face (remhos_tools.cpp:915-973, neighbour traces read like
+ * rmh_lo_upwind's, 0 on the domain boundary), the element redistribution of the remainder and, when mass_lim != 0, the mass iteration
+ * (at most 101 passes, exit at a residual norm <= 1e-8) with the element's consistent mass matrix -- on the mesh at the pseudo-time of
+ * the last rmh_setup.  xi_min / xi_max: the dof bounds of u (rmh_elem_minmax + rmh_bounds); the element extrema of u are taken inside
+ * the kernel.  scale: DEVICE array [ne], scale(e) = vmax_e / (2 sqrt(dim) h_e / order) of the initial mesh (remhos_mono.cpp:37-57;
+ * rmhd_case_mono_scale of rmh_driver.h); not read when mass_lim = 0, but it must not be NULL.  Divides by the context's lumped
+ * mass: the one rmh_ho_apply left since the last rmh_setup, otherwise it is formed first.  No atomics: the same bits from run to
+ * run.  Contexts with ghost elements return RMH_ERR_INVALID (one block).  dim = 2: every order.  dim = 3: orders 1 to 3 with
+ * mass_lim, every order without -- order >= 4 with mass_lim returns RMH_ERR_INVALID with a message naming -mono 1 and the order (the
+ * element's mass matrix must stay in the LDS over the passes).
+ * rmh_last_mono: of the last rmh_mono_rd call, the largest number of passes an element's mass iteration took (0 without mass_lim)
+ * and the number of elements that left the loop at the cap of 101 passes with a residual above the tolerance.
+ * rmh_mono_passes: the passes of every element (HOST array [ne]); negative: the element left the loop at the cap.  Both synchronise;
+ * RMH_ERR_STATE before the first rmh_mono_rd call. */
+int rmh_mono_rd(rmh_ctx *ctx, const double *u, const double *xi_min, const double *xi_max, const double *scale, int mass_lim,
+                double *du);
+int rmh_last_mono(rmh_ctx *ctx, int *iters_max, long long *n_not_converged);
+int rmh_mono_passes(rmh_ctx *ctx, int *passes);
 
 /* ---- Product-field remap (-ps; second block of AdvectionOperator::LimitMult, remhos.cpp:1848-1915) ----------------
  * Flags are device byte arrays (mfem::Array<bool>): active_el[ne], active_dofs[ne * ndof].

@@ -62,6 +62,11 @@ typedef struct {
                          (remhos_fct.cpp:155-181, 295-446: like 4, and one block, no pa -- remhos.cpp:1088).  lo_type 1
                          (DiscreteUpwind, remhos_lo.cpp:31-100) has the same conditions as fct_type 1, except pa; so has
                          lo_type 2 (the same solver with M_L M^-1 C, remhos.cpp:749-771), dim = 3: order <= 3.               */
+   int mono_type;     /* -mono: 0 off; 1 MonoRDSolver without subcells (MonolithicSolverType::ResDistMono, remhos_mono.cpp:60-356,
+                         remhos.cpp:997-1013): the whole right-hand side of a stage is one rmh_mono_rd call with mass_lim = 1, run
+                         through RK3 SSP with no LimitMult (remhos.cpp:1687); ho_type, lo_type and fct_type are ignored like in the
+                         reference.  rmhd_run / rmhd_run_state on one block, fused = 0, no -ps; -bt 0|1, -vb and -save apply;
+                         dim = 3: order <= 3.  2 (ResDistMonoSubcell) and a smoothness indicator (-si) are refused.             */
 } rmhd_config;
 
 typedef struct {
@@ -86,6 +91,7 @@ const double *rmhd_case_vel(const rmhd_case *c);         /* [ne_owned][3][27] */
 const double *rmhd_case_u0(const rmhd_case *c);          /* [ne_owned][ndof]  */
 const double *rmhd_case_s0(const rmhd_case *c);          /* [ne_owned][ndof] s0_function at the nodes (-ps, remhos.cpp:892-894) */
 const double *rmhd_case_subcell_vel(const rmhd_case *c); /* [ne_owned][3][ndof] or NULL */
+const double *rmhd_case_mono_scale(rmhd_case *c);        /* [ne_owned] scale(e) of MonoRDSolver's constructor (remhos_mono.cpp:37-57), made on first use */
 const int *rmhd_case_face_nbr(const rmhd_case *c);       /* [ne_owned][6]  */
 const int *rmhd_case_stencil27(const rmhd_case *c);      /* [ne_owned][27] */
 const long long *rmhd_case_owned_gid(const rmhd_case *c);

@@ -16,7 +16,7 @@ SYMBOLS = [
     "rmh_create", "rmh_destroy", "rmh_last_error", "rmh_version", "rmh_set_stream", "rmh_stream_create_reserving", "rmh_stream_destroy", "rmh_batch_order", "rmh_setup",
     "rmh_set_ghost_u", "rmh_set_ghost_minmax", "rmh_halo_pack", "rmh_ho_apply", "rmh_ho_neumann", "rmh_last_neumann", "rmh_lumped_mass",
     "rmh_compute_lumped_mass", "rmh_lo_massavg", "rmh_lo_rdsubcell", "rmh_lo_rd", "rmh_elem_minmax", "rmh_bounds",
-    "rmh_fct_clipscale", "rmh_fct_projection", "rmh_lo_upwind", "rmh_lo_upwind_prec", "rmh_fct_fluxbased", "rmh_limit_fused", "rmh_limit_fused_lo", "rmh_stage_fused", "rmh_stage_fused_range", "rmh_stage_fused_chain",
+    "rmh_fct_clipscale", "rmh_fct_projection", "rmh_lo_upwind", "rmh_lo_upwind_prec", "rmh_mono_rd", "rmh_last_mono", "rmh_mono_passes", "rmh_fct_fluxbased", "rmh_limit_fused", "rmh_limit_fused_lo", "rmh_stage_fused", "rmh_stage_fused_range", "rmh_stage_fused_chain",
     "rmh_halo_pack_records", "rmh_set_ghost_records", "rmh_timers", "rmh_reset_timers", "rmh_enable_timers",
     "rmh_last_cg_iters", "rmh_set_mass_tol", "rmh_get_mass_tol", "rmh_set_mass_completion", "rmh_set_lo_type", "rmh_set_bounds_type", "rmh_set_dt_control",
     "rmh_dt_estimate_reset", "rmh_dt_estimate_update", "rmh_dt_estimate_get", "rmh_invalidate_extrema",
@@ -115,6 +115,9 @@ def load_library(path: str | None = None) -> C.CDLL:
     lib.rmh_fct_projection.argtypes = [p, p, p, p, p, p, p, d, p]
     lib.rmh_lo_upwind.argtypes = [p, p, p]
     lib.rmh_lo_upwind_prec.argtypes = [p, p, p]
+    lib.rmh_mono_rd.argtypes = [p, p, p, p, p, i, p]
+    lib.rmh_last_mono.argtypes = [p, C.POINTER(i), C.POINTER(C.c_longlong)]
+    lib.rmh_mono_passes.argtypes = [p, p]
     lib.rmh_ho_neumann.argtypes = [p, p, p]
     lib.rmh_last_neumann.argtypes = [p, C.POINTER(i), C.POINTER(d * 20)]
     lib.rmh_fct_fluxbased.argtypes = [p, p, p, p, p, p, p, d, p]
@@ -288,6 +291,25 @@ class Context:
     def lo_upwind_prec(self, u, du_lo):
         """DiscreteUpwind with the preconditioned matrix M_L M^-1 C (-lo 2) at the geometry of the last setup(t)"""
         self._check(self.lib.rmh_lo_upwind_prec(self.h, _ptr(u), _ptr(du_lo)))
+
+    def mono_rd(self, u, xi_min, xi_max, scale, mass_lim, du):
+        """MonoRDSolver (-mono 1, no subcells, no smoothness indicator) at the geometry of the last setup(t): the whole right-hand
+        side of a stage; xi_min / xi_max the dof bounds of u, scale [ne] (Case.mono_scale), mass_lim: with the mass iteration"""
+        self._check(self.lib.rmh_mono_rd(self.h, _ptr(u), _ptr(xi_min), _ptr(xi_max), _ptr(scale), int(mass_lim), _ptr(du)))
+
+    def last_mono(self):
+        """(largest pass count of an element's mass iteration, elements that left it at the cap) of the last mono_rd; synchronises"""
+        n, bad = C.c_int(0), C.c_longlong(0)
+        self._check(self.lib.rmh_last_mono(self.h, C.byref(n), C.byref(bad)))
+        return n.value, bad.value
+
+    def mono_passes(self):
+        """passes of every element's mass iteration in the last mono_rd (negative: left at the cap), a host int32 array"""
+        import numpy as np
+
+        out = np.zeros(self.ne, dtype=np.int32)
+        self._check(self.lib.rmh_mono_passes(self.h, out.ctypes.data))
+        return out
 
     def ho_neumann(self, u, du):
         """NeumannHOSolver (-ho 1) at the geometry of the last setup(t): at most 20 lumped-mass updates, the reference's global

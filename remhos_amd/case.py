@@ -13,7 +13,7 @@ HOST_LIB_PATH = os.path.join(_HERE, "librmh_host.so")
 
 DRIVER_SYMBOLS = [
     "rmhd_case_create", "rmhd_case_destroy", "rmhd_last_error", "rmhd_case_get_info", "rmhd_case_x0",
-    "rmhd_case_vel", "rmhd_case_u0", "rmhd_case_s0", "rmhd_case_subcell_vel", "rmhd_case_face_nbr", "rmhd_case_stencil27",
+    "rmhd_case_vel", "rmhd_case_u0", "rmhd_case_s0", "rmhd_case_subcell_vel", "rmhd_case_mono_scale", "rmhd_case_face_nbr", "rmhd_case_stencil27",
     "rmhd_case_owned_gid", "rmhd_case_ghost_gid", "rmhd_case_peer", "rmhd_case_save", "rmhd_run", "rmhd_run_state", "rmhd_run_rank", "rmhd_run_partitioned", "rmhd_id_file_exchange", "rmhd_axpby",
 ]
 
@@ -26,7 +26,7 @@ class RmhdConfig(C.Structure):
         ("bounds_type", C.c_int), ("dt_control", C.c_int), ("ho_type", C.c_int), ("save", C.c_int),
         ("rs_extra", C.c_int * 3), ("pa", C.c_int), ("self_wrap", C.c_int), ("warmup_steps", C.c_int),
         ("ps", C.c_int), ("ode_solver", C.c_int), ("tile_rows", C.c_int), ("verify_bounds", C.c_int),
-        ("fct_type", C.c_int),
+        ("fct_type", C.c_int), ("mono_type", C.c_int),
     ]
 
 
@@ -57,7 +57,7 @@ class RmhdResult(C.Structure):
 
 def make_config(mesh="periodic-cube", rs=1, order=3, problem=10, dt=-1.0, t_final=0.5, max_steps=-1, lo_type=5,
                 fused=1, part=(1, 1, 1), rank=0, bounds_type=0, dt_control=0, ho_type=3, save=0,
-                rs_extra=(0, 0, 0), pa=0, self_wrap=0, warmup_steps=0, ps=0, ode_solver=3, tile_rows=0, verify_bounds=0, fct_type=0) -> RmhdConfig:
+                rs_extra=(0, 0, 0), pa=0, self_wrap=0, warmup_steps=0, ps=0, ode_solver=3, tile_rows=0, verify_bounds=0, fct_type=0, mono_type=0) -> RmhdConfig:
     c = RmhdConfig()
     c.mesh = mesh.encode()
     c.rs, c.order, c.problem = rs, order, problem
@@ -73,6 +73,7 @@ def make_config(mesh="periodic-cube", rs=1, order=3, problem=10, dt=-1.0, t_fina
     c.tile_rows = int(tile_rows)
     c.verify_bounds = int(verify_bounds)
     c.fct_type = int(fct_type)  # 0 / 2 clip + scale, 4 element FCT projection, 1 flux-based FCT (fused = 0)
+    c.mono_type = int(mono_type)  # 0 off, 1 MonoRDSolver (-mono 1: one block, fused = 0; ho / lo / fct types are ignored)
     return c
 
 
@@ -88,7 +89,7 @@ def bind_driver(lib: C.CDLL) -> C.CDLL:
     if hasattr(lib, "rmhd_axpby"):  # (device library only: librmh_host.so has no kernels)
         lib.rmhd_axpby.argtypes = [C.c_double, p, C.c_double, p, p, C.c_longlong, p]
         lib.rmhd_axpby.restype = C.c_int
-    for name in ("x0", "vel", "u0", "s0", "subcell_vel", "face_nbr", "stencil27", "owned_gid", "ghost_gid"):
+    for name in ("x0", "vel", "u0", "s0", "subcell_vel", "mono_scale", "face_nbr", "stencil27", "owned_gid", "ghost_gid"):
         f = getattr(lib, "rmhd_case_" + name)
         f.argtypes = [p]
         f.restype = p
@@ -156,6 +157,15 @@ class Case:
             self.peers.append((rank.value, _view(ps.value, (ns.value,), np.int32), _view(pr.value, (nr.value,), np.int32)))
         lib.rmhd_case_destroy(h)
         self._lib = lib
+
+    def mono_scale(self):
+        """scale(e) of MonoRDSolver's constructor (-mono 1; remhos_mono.cpp:37-57) on the initial mesh, [ne_owned]"""
+        lib = self._lib
+        h = lib.rmhd_case_create(C.byref(self.cfg))
+        try:
+            return _view(lib.rmhd_case_mono_scale(h), (self.ne_owned,), np.float64)
+        finally:
+            lib.rmhd_case_destroy(h)
 
     def save(self, t, u, mesh_path, gf_path=None):
         """-save (remhos.cpp:1015-1030, 1365-1380): MFEM mesh at pseudo-time t (+ GridFunction of the host array u)."""

@@ -1,7 +1,8 @@
 // remhos_amd -- command-line front end of the single-GPU driver (rmhd_run), accepting the subset of
 // the reference's flags that select the hot path (remhos.cpp:249-334) and printing the same report
 // lines (remhos.cpp:1423-1428, 1938-1952):
-//   remhos_amd -m periodic-cube -p 10 -rs 4 -o 3 -dt -1 -tf 0.5 -ms 20 -ho 3 -lo 5 -fct 2 -pa [-bt 1 -dtc 1]   (-fct 4: element FCT projection, -ho 1 / -lo 1 / -lo 2 / -fct 1: NeumannHOSolver / DiscreteUpwind / its preconditioned form / FluxBasedFCT; granular sequence)
+//   remhos_amd -m periodic-cube -p 10 -rs 4 -o 3 -dt -1 -tf 0.5 -ms 20 -ho 3 -lo 5 -fct 2 -pa [-bt 1 -dtc 1]   (-fct 4: element FCT projection, -ho 1 / -lo 1 / -lo 2 / -fct 1: NeumannHOSolver / DiscreteUpwind / its preconditioned form / FluxBasedFCT; granular sequence;
+//   -mono 1: MonoRDSolver, the whole stage as one monolithic residual-distribution update -- -ho / -lo / -fct are then ignored)
 #include "../../include/rmh_driver.h"
 
 #include <cstdio>
@@ -59,8 +60,27 @@ int main(int argc, char **argv)
       else if (a == "-ps") { c.ps = 1; }
       else if (a == "-vb") { c.verify_bounds = 1; } // remhos.cpp:324
       else if (a == "-no-vb") { c.verify_bounds = 0; }
+      else if (a == "-mono") { c.mono_type = std::atoi(next()); } // remhos.cpp:292-296: 0 off, 1 ResDistMono; 2 ResDistMonoSubcell is refused
+      else if (a == "-si")
+      {
+         std::fprintf(stderr, "remhos_amd: -si (smoothness indicator) is not built\n");
+         return 1;
+      }
       else if (a == "-tile") { c.tile_rows = std::atoi(next()); } // element numbering of the case builder (rmh_driver.h)
       else { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return 1; }
+   }
+   if (c.mono_type != 0 && c.mono_type != 1)
+   {
+      std::fprintf(stderr, "remhos_amd implements -mono 1 (MonoRDSolver without subcells); -mono %d is not built\n", c.mono_type);
+      return 1;
+   }
+   if (c.mono_type == 1)
+   {
+      // the monolithic solver replaces the HO / LO / FCT split (remhos.cpp:1687): those options take their defaults, the solver classes run
+      ho = 3;
+      fct = 2;
+      c.lo_type = 5;
+      c.fused = 0;
    }
    if ((ho != 1 && ho != 2 && ho != 3) || (fct != 1 && fct != 2 && fct != 4) || c.lo_type < 1 || c.lo_type > 5)
    {

@@ -9,6 +9,7 @@
 #include "rmh_upwind.hpp"
 #include "rmh_pdu.hpp"
 #include "rmh_neumann.hpp"
+#include "rmh_mono.hpp"
 #include "rmh_product2d.hpp"
 
 #include <algorithm>
@@ -498,6 +499,14 @@ void launch_lo_upwind_prec(rmh_ctx *c, const UpwArgs &a, const double *u, double
                       (const double *)c->d_m, du_lo);
 }
 
+template <int P, int DIM>
+void launch_mono_rd(rmh_ctx *c, const UpwArgs &a, const double *u, const double *xi_min, const double *xi_max, const double *scale,
+                    int mass_lim, double *du)
+{
+   hipLaunchKernelGGL((mono_rd_kernel<P, DIM>), dim3(c->ne), dim3(EfpCfg<P, DIM>::NT), 0, c->stream, a, u, (const double *)c->d_m,
+                      xi_min, xi_max, scale, mass_lim, du, c->d_mono_rec);
+}
+
 // first pass (20 updates, the elements' residual norms), the global norms and the stopping check K, second pass (K - 1 updates)
 template <int P, int DIM>
 void launch_neumann_iter(rmh_ctx *c, double *du)
@@ -666,7 +675,7 @@ void rmh_destroy(rmh_ctx *c)
    if (!c) { return; }
    (void)hipSetDevice(c->device);
    exchange_free(c);
-   void *bufs[] = {c->d_x0, c->d_vel, c->d_x0h, c->d_velh, c->d_tab, c->d_subvel, c->d_subx0, c->d_subvmid, c->d_fgeo, c->d_face_rows, c->d_m, c->d_scr_ho, c->d_scr_lo, c->d_xe_min, c->d_xe_max, c->d_xe_min2, c->d_xe_max2, c->d_nbr, c->d_st27, c->d_cg, c->d_dt_est, c->d_viol, c->d_nm_rhs, c->d_nm_wdet, c->d_nm_part, c->d_nm_norms, c->d_nm_ctl};
+   void *bufs[] = {c->d_x0, c->d_vel, c->d_x0h, c->d_velh, c->d_tab, c->d_subvel, c->d_subx0, c->d_subvmid, c->d_fgeo, c->d_face_rows, c->d_m, c->d_scr_ho, c->d_scr_lo, c->d_xe_min, c->d_xe_max, c->d_xe_min2, c->d_xe_max2, c->d_nbr, c->d_st27, c->d_cg, c->d_dt_est, c->d_viol, c->d_nm_rhs, c->d_nm_wdet, c->d_nm_part, c->d_nm_norms, c->d_nm_ctl, c->d_mono_rec};
    for (void *b : bufs) { (void)hipFree(b); }
    for (int b = 0; b < 4; b++)
    {
@@ -933,6 +942,62 @@ int rmh_lo_upwind_prec(rmh_ctx *c, const double *u, double *du_lo)
       }
       return 0;
    });
+}
+
+int rmh_mono_rd(rmh_ctx *c, const double *u, const double *xi_min, const double *xi_max, const double *scale, int mass_lim, double *du)
+{
+   if (!c || !u || !xi_min || !xi_max || !scale || !du) { return fail(RMH_ERR_INVALID, "null argument"); }
+   if (c->ng > 0)
+   {
+      return fail(RMH_ERR_INVALID, "rmh_mono_rd (-mono 1): contexts with ghost elements are not supported (the solver runs on one block)");
+   }
+   if (mass_lim && c->dim == 3 && c->p >= 4)
+   {
+      return fail(RMH_ERR_INVALID, "rmh_mono_rd (-mono 1): order " + std::to_string(c->p) +
+                                      " in 3-D with mass_lim is not supported: the element's mass matrix must stay in the LDS over the passes (orders 1 to 3 in 3-D, 1 to 6 in 2-D; every order without mass_lim)");
+   }
+   RMH_ENTER(c);
+   extrema_dropped(c);
+   if (!c->d_mono_rec) { RMH_HIP(hipMalloc((void **)&c->d_mono_rec, (size_t)c->ne * sizeof(int))); }
+   if (int rc = ensure_lumped_mass(c)) { return rc; }
+   const UpwArgs a = upwind_args(c);
+   return timed(c, 0, [&]() -> int {
+      RMH_DISPATCH_PD(c, (launch_mono_rd<P, DIM>(c, a, u, xi_min, xi_max, scale, mass_lim ? 1 : 0, du)));
+      return 0;
+   });
+}
+
+// the per-element record of the last rmh_mono_rd call, on the host
+static int mono_record(rmh_ctx *c, std::vector<int> &rec, const char *who)
+{
+   if (!c->d_mono_rec) { return fail(RMH_ERR_STATE, std::string(who) + ": no rmh_mono_rd call on this context"); }
+   RMH_ENTER(c);
+   RMH_HIP(hipStreamSynchronize(c->stream));
+   rec.resize(c->ne);
+   RMH_HIP(hipMemcpy(rec.data(), c->d_mono_rec, (size_t)c->ne * sizeof(int), hipMemcpyDeviceToHost));
+   return RMH_OK;
+}
+
+int rmh_last_mono(rmh_ctx *c, int *iters_max, long long *n_not_converged)
+{
+   if (!c || !iters_max || !n_not_converged) { return fail(RMH_ERR_INVALID, "null argument"); }
+   std::vector<int> rec;
+   if (int rc = mono_record(c, rec, "rmh_last_mono")) { return rc; }
+   int mx = 0;
+   long long bad = 0;
+   for (int v : rec) { mx = std::max(mx, std::abs(v)); bad += v < 0; }
+   *iters_max = mx;
+   *n_not_converged = bad;
+   return RMH_OK;
+}
+
+int rmh_mono_passes(rmh_ctx *c, int *passes)
+{
+   if (!c || !passes) { return fail(RMH_ERR_INVALID, "null argument"); }
+   std::vector<int> rec;
+   if (int rc = mono_record(c, rec, "rmh_mono_passes")) { return rc; }
+   std::copy(rec.begin(), rec.end(), passes);
+   return RMH_OK;
 }
 
 int rmh_ho_neumann(rmh_ctx *c, const double *u, double *du)

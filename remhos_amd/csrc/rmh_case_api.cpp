@@ -13,6 +13,8 @@
 struct rmhd_case
 {
    remhos::CaseData d;
+   int problem = 0;
+   std::vector<double> mono_scale; // made on first use (rmhd_case_mono_scale)
 };
 
 namespace remhos
@@ -56,6 +58,7 @@ rmhd_case *rmhd_case_create(const rmhd_config *cfg)
       delete c;
       return nullptr;
    }
+   c->problem = cfg->problem;
    return c;
 }
 
@@ -93,6 +96,12 @@ const double *rmhd_case_s0(const rmhd_case *c) { return c->d.s0.data(); }
 const double *rmhd_case_subcell_vel(const rmhd_case *c)
 {
    return c->d.subcell_vel.empty() ? nullptr : c->d.subcell_vel.data();
+}
+const double *rmhd_case_mono_scale(rmhd_case *c)
+{
+   if (!c) { return nullptr; }
+   if (c->mono_scale.empty()) { c->mono_scale = remhos::mono_scale(c->d, c->problem); }
+   return c->mono_scale.data();
 }
 const int *rmhd_case_face_nbr(const rmhd_case *c) { return c->d.face_nbr.data(); }
 const int *rmhd_case_stencil27(const rmhd_case *c) { return c->d.stencil27.data(); }

@@ -79,7 +79,8 @@ struct rmh_ctx
    // the elements' squared residual norms [20][ne], the 20 global norms and the control words of rmh_neumann.hpp
    double *d_nm_rhs = nullptr, *d_nm_wdet = nullptr, *d_nm_part = nullptr, *d_nm_norms = nullptr;
    int *d_nm_ctl = nullptr;
-   int lo_type = 5;    // LO solver inside rmh_stage_fused: 5 mass-based average, 4 subcell residual distribution
+   int *d_mono_rec = nullptr; // rmh_mono_rd (made on first use): the passes of every element's mass iteration in the last call
+   int lo_type = 5;   // LO solver inside rmh_stage_fused: 5 mass-based average, 4 subcell residual distribution
    // stopwatches (TimingData, remhos_tools.hpp:52-64)
    bool timers_on = false;
    double tacc[4] = {0, 0, 0, 0};

@@ -257,6 +257,41 @@ void FluxBasedFCT::CalcFCTProduct(const ParGridFunction &, const Vector &, const
    RMH_VERIFY(false, "Product remap (-ps) is not implemented for FluxBasedFCT (-fct 1)");
 }
 
+MonoRDSolver::MonoRDSolver(ParFiniteElementSpace &space, DofInfo &dofs_, SmoothnessIndicator *si, const double *scale_host,
+                           bool subcell, bool timedep, bool masslim)
+   : MonolithicSolver(space), dofs(dofs_), smth_indicator(si), scale(space.GetNE()), subcell_scheme(subcell), time_dep(timedep),
+     mass_lim(masslim)
+{
+   RMH_VERIFY(!subcell, "MonoRDSolver: the subcell scheme (-mono 2) is not built");
+   RMH_VERIFY(si == NULL, "MonoRDSolver: the smoothness indicator (-si) is not built");
+   RMH_VERIFY(scale_host, "MonoRDSolver: scale not given");
+   scale.CopyFromHost(scale_host);
+}
+
+void MonoRDSolver::CalcSolution(const Vector &u, Vector &du) const
+{
+   // remhos_mono.cpp:84-99 (the element extrema again inside the kernel), :108-355
+   dofs.ComputeElementsMinMax(u, dofs.xe_min, dofs.xe_max);
+   dofs.ComputeBounds(dofs.xe_min, dofs.xe_max, dofs.xi_min, dofs.xi_max);
+   RMH_CALL(rmh_mono_rd(pfes.Ctx(), u.Read(), dofs.xi_min.Read(), dofs.xi_max.Read(), scale.Read(), mass_lim ? 1 : 0, du.Write()));
+}
+
+// -mono of rmhd_config: 0 on success, else the message is in g_driver_error
+static int check_mono_type(const rmhd_config *cfg, bool partitioned)
+{
+   const int mono = cfg->mono_type;
+   if (mono == 0) { return 0; }
+   if (mono == 2) { g_driver_error = "mono_type 2 (-mono 2): the subcell variant of the monolithic RD solver (ResDistMonoSubcell) is not built"; return -1; }
+   if (mono != 1) { g_driver_error = "mono_type must be 0 (off) or 1 (-mono 1, MonoRDSolver): got " + std::to_string(mono); return -1; }
+   if (partitioned || cfg->px * cfg->py * cfg->pz > 1) { g_driver_error = "mono_type 1 (-mono 1): partitioned runs are not built for the monolithic RD solver (one block, rmhd_run with fused = 0)"; return -1; }
+   if (cfg->self_wrap) { g_driver_error = "mono_type 1 (-mono 1): a self-wrapped block (self_wrap) has ghost elements, which rmh_mono_rd does not take"; return -1; }
+   if (cfg->fused) { g_driver_error = "mono_type 1 (-mono 1): the fused limiter and the one-kernel stage are the HO / LO / FCT split the monolithic solver replaces (fused must be 0)"; return -1; }
+   if (cfg->ps) { g_driver_error = "mono_type 1 (-mono 1) with -ps: product remap (ps) is not built for the monolithic RD solver"; return -1; }
+   if (cfg->ode_solver != 0 && cfg->ode_solver != 3) { g_driver_error = "mono_type 1 (-mono 1): runs through RK3 SSP (-s 3); the IDP solvers limit a rate the monolithic solver does not have"; return -1; }
+   if (cfg->dt_control) { g_driver_error = "mono_type 1 (-mono 1) with -dtc: the time step estimate is formed from the LO solution, which the monolithic solver does not have"; return -1; }
+   return 0;
+}
+
 // -fct of rmhd_config: what the entry points below accept (0 on success, else the message is in g_driver_error)
 static int check_fct_type(const rmhd_config *cfg, bool partitioned)
 {
@@ -388,8 +423,15 @@ void AdvectionOperator::MultUnlimited(const Vector &X, Vector &Y) const
    // remap: move the mesh to the stage time and re-set-up M_HO, K_HO, lumpedM
    // (remhos.cpp:1598-1637) -- matrix-free here: the kernels evaluate x0 + t*v themselves
    RMH_CALL(rmh_setup(pfes.Ctx(), GetTime()));
-   RMH_VERIFY(ho_solver && lo_solver && fct_solver, "FCT requires HO and LO solvers."); // remhos.cpp:1690
    const int n = pfes.GetVSize();
+   if (mono_solver) // remhos.cpp:1687
+   {
+      const Vector u(const_cast<double *>(X.Read()), n);
+      Vector d_u(Y.Write(), n);
+      mono_solver->CalcSolution(u, d_u);
+      return;
+   }
+   RMH_VERIFY(ho_solver && lo_solver && fct_solver, "FCT requires HO and LO solvers."); // remhos.cpp:1690
    if (product)
    {
       // Remap the product field (remhos.cpp:1709-1738).  Its HO rate is formed FIRST: the context keeps the element
@@ -406,6 +448,7 @@ void AdvectionOperator::MultUnlimited(const Vector &X, Vector &Y) const
 
 void AdvectionOperator::LimitMult(const Vector &X, Vector &Y) const
 {
+   if (mono_solver) { return; } // (the monolithic solver's result is final: the reference's Mult has no limiting step either)
    const int n = pfes.GetVSize();
    const Vector u(const_cast<double *>(X.Read()), n);
    Vector d_u(Y.Write(), n);
@@ -625,6 +668,18 @@ extern "C" int rmhd_run_rank(const rmhd_config *cfg, const char *comm_id_file, i
 {
    if (!cfg || !res) { g_driver_error = "null argument"; return -1; }
    std::memset(res, 0, sizeof(*res));
+   if (check_mono_type(cfg, false) != 0) { return -1; }
+   rmhd_config mono_cfg;
+   if (cfg->mono_type)
+   {
+      // -ho, -lo and -fct are ignored beside -mono, as in the reference (remhos.cpp:1687): they take their defaults here
+      mono_cfg = *cfg;
+      mono_cfg.ho_type = 0;
+      mono_cfg.lo_type = 5;
+      mono_cfg.fct_type = 0;
+      mono_cfg.pa = 0;
+      cfg = &mono_cfg;
+   }
    if (check_fct_type(cfg, false) != 0) { return -1; }
    CaseConfig cc = to_config(*cfg);
    const int nranks = cc.px * cc.py * cc.pz;
@@ -641,6 +696,12 @@ extern "C" int rmhd_run_rank(const rmhd_config *cfg, const char *comm_id_file, i
    if (cc.lo_type == 2 && cd.dim == 3 && cd.order >= 4)
    {
       g_driver_error = "lo_type 2 (-lo 2): order " + std::to_string(cd.order) + " in 3-D is not supported: the element's dense matrices must fit the LDS (orders 1 to 3 in 3-D, 1 to 6 in 2-D)";
+      return -1;
+   }
+
+   if (cfg->mono_type && cd.dim == 3 && cd.order >= 4)
+   {
+      g_driver_error = "mono_type 1 (-mono 1): order " + std::to_string(cd.order) + " in 3-D is not supported: the element's mass matrix must stay in the LDS over the passes of the mass iteration (orders 1 to 3 in 3-D, 1 to 6 in 2-D)";
       return -1;
    }
 
@@ -775,6 +836,15 @@ extern "C" int rmhd_run_rank(const rmhd_config *cfg, const char *comm_id_file, i
          if (cfg->ho_type == 2) { RMH_CALL(rmh_set_mass_tol(ctx, 1e-12, 0.0, 500)); }
       }
       AdvectionOperator adv(pfes, dofs, ho_solver, lo_solver, fct_solver, (ps || idp) && cfg->fused != 0 && cc.lo_type == 5, ps);
+      // Setup of the monolithic solver (if any): remhos.cpp:997-1006; mass_lim: :999
+      MonolithicSolver *mono_solver = nullptr;
+      if (cfg->mono_type == 1)
+      {
+         const std::vector<double> scale = mono_scale(cd, cc.problem);
+         const bool mass_lim = cc.problem != 6 && cc.problem != 7;
+         mono_solver = new MonoRDSolver(pfes, dofs, nullptr, scale.data(), false, cd.exec_mode == 1, mass_lim);
+         adv.mono_solver = mono_solver;
+      }
       const bool vb = cfg->verify_bounds != 0;
       adv.verify_bounds = vb;         // remhos.cpp:1115-1116
       fct_solver->verify_bounds = vb;
@@ -1058,6 +1128,7 @@ extern "C" int rmhd_run_rank(const rmhd_config *cfg, const char *comm_id_file, i
       res->cg_iters_max = it;
       res->repeats = repeats;
       delete ode_solver_p;
+      delete mono_solver;
       delete fct_solver;
       delete lo_solver;
       delete ho_solver;
@@ -1162,6 +1233,7 @@ extern "C" int rmhd_run_partitioned(const rmhd_config *cfg, const char *comm_id_
    CaseConfig cc0 = to_config(*cfg);
    const int nranks = cc0.px * cc0.py * cc0.pz;
    const bool rccl = comm_id_file && comm_id_file[0];
+   if (check_mono_type(cfg, true) != 0) { return -1; }
    if (check_fct_type(cfg, true) != 0) { return -1; }
    if (!cfg->fused) { g_driver_error = "rmhd_run_partitioned runs the one-kernel stage (fused = 1)"; return -1; }
    std::vector<Block> blocks(rccl ? 1 : nranks);

@@ -861,6 +861,65 @@ void gauss_legendre_01(int n, std::vector<double> &x, std::vector<double> &w)
 }
 } // namespace
 
+// MonoRDSolver's constructor (remhos_mono.cpp:37-57): scale(e) = vmax_e / (2 sqrt(dim) h_e / order) on the INITIAL mesh, vmax_e the
+// largest |velocity| over the points of the rule of order OrderW + 2 p + 2 OrderGrad(el) = 6 dim + 4 p - 7 for a Q2 tensor element
+// (OrderW = 2 dim - 1, OrderGrad(el) = 2 dim + p - 3: the orders rmh_pdu.hpp uses), order / 2 + 1 Gauss-Legendre points a direction,
+// and h_e = |det J(centre)|^(1 / dim) [MFEM: Mesh::GetElementSize].  The velocity is the analytic velocity_function of the
+// problem in both modes, not the remap displacement.  MFEM's rule and element size are restated from its documentation and are
+// not verified against a build of the reference.
+std::vector<double> mono_scale(const CaseData &d, int problem)
+{
+   const int dim = d.dim, p = d.order, nn = dim == 3 ? 27 : 9;
+   const int nq = (6 * dim + 4 * p - 7) / 2 + 1;
+   std::vector<double> xq, wq;
+   gauss_legendre_01(nq, xq, wq);
+   std::vector<double> L((size_t)nq * 3);
+   for (int q = 0; q < nq; q++) { lag2(xq[q], &L[3 * q]); }
+   const double Lc[3] = {0.0, 1.0, 0.0}, dLc[3] = {-1.0, 0.0, 1.0}; // the Q2 basis and its derivative at 1/2
+   std::vector<double> scale(d.ne_owned);
+   parallel_for(d.ne_owned, [&](long long e0, long long e1)
+   {
+      for (long long e = e0; e < e1; e++)
+      {
+         const double *X = &d.x0[(size_t)e * dim * nn];
+         double vmax = 0.0;
+         const int nqz = dim == 3 ? nq : 1;
+         for (int qz = 0; qz < nqz; qz++)
+         {
+            for (int qy = 0; qy < nq; qy++)
+            {
+               for (int qx = 0; qx < nq; qx++)
+               {
+                  double x[3] = {0, 0, 0}, v[3] = {0, 0, 0};
+                  for (int a = 0; a < nn; a++)
+                  {
+                     const double w = L[3 * qx + a % 3] * L[3 * qy + (a / 3) % 3] * (dim == 3 ? L[3 * qz + a / 9] : 1.0);
+                     for (int c = 0; c < dim; c++) { x[c] += w * X[c * nn + a]; }
+                  }
+                  if (dim == 3) { velocity_function(problem, d.bb_min, d.bb_max, x, v); }
+                  else { velocity_function_2d(problem, d.bb_min, d.bb_max, x, v); }
+                  vmax = std::max(vmax, std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]));
+               }
+            }
+         }
+         double J[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
+         for (int a = 0; a < nn; a++)
+         {
+            const int ax = a % 3, ay = (a / 3) % 3, az = a / 9;
+            const double lz = dim == 3 ? Lc[az] : 1.0;
+            const double g[3] = {dLc[ax] * Lc[ay] * lz, Lc[ax] * dLc[ay] * lz, dim == 3 ? Lc[ax] * Lc[ay] * dLc[az] : 0.0};
+            for (int c = 0; c < dim; c++) { for (int k = 0; k < dim; k++) { J[c][k] += g[k] * X[c * nn + a]; } }
+         }
+         if (dim == 2) { J[0][2] = J[1][2] = J[2][0] = J[2][1] = 0.0; J[2][2] = 1.0; }
+         const double det = J[0][0] * (J[1][1] * J[2][2] - J[1][2] * J[2][1]) - J[0][1] * (J[1][0] * J[2][2] - J[1][2] * J[2][0]) +
+                            J[0][2] * (J[1][0] * J[2][1] - J[1][1] * J[2][0]);
+         const double h = std::pow(std::fabs(det), 1.0 / dim);
+         scale[e] = vmax / (2.0 * (std::sqrt((double)dim) * h / p));
+      }
+   });
+   return scale;
+}
+
 std::string lp_error_sums(const CaseData &d, int problem, double t_exact, const double *u, double err[3])
 {
    err[0] = err[1] = err[2] = 0.0;

@@ -81,6 +81,9 @@ double u0_function_2d(int problem, const double *bb_min, const double *bb_max, c
 // |e| w, sum of e^2 w, max |e|).  Returns "" or why the problem has no exact solution here.
 std::string lp_error_sums(const CaseData &d, int problem, double t_exact, const double *u, double err[3]);
 
+// scale(e) of MonoRDSolver's constructor (-mono 1; remhos_mono.cpp:37-57) on the initial mesh of the case, [ne_owned]
+std::vector<double> mono_scale(const CaseData &d, int problem);
+
 // MFEM text formats of the mesh at pseudo-time t and of a DG field (host pointer); "" on success
 std::string save_mfem(const CaseData &d, double t, const double *u, const char *mesh_path, const char *gf_path);
 
