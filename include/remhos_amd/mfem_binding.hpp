@@ -9,6 +9,7 @@
 #pragma once
 #include "../rmh.h"
 
+#include <algorithm>
 #include <vector>
 
 namespace mfem
@@ -33,12 +34,13 @@ struct RMHContext
    {
       Mesh &mesh = *pfes.GetMesh();
       const int dim = mesh.Dimension();
-      // 3: hexahedra (the whole API); 2: quadrilaterals (HO / LO solvers and the granular limiter sequence, rmh.h "dim = 2")
-      MFEM_VERIFY(dim == 3 || dim == 2, "the MI355X hot path is built for hexahedral and quadrilateral tensor-lattice meshes");
+      // 3: hexahedra (the whole API); 2: quadrilaterals (HO / LO solvers and the granular limiter sequence, rmh.h "dim = 2");
+      // 1: segments (rmh.h "dim = 1")
+      MFEM_VERIFY(dim >= 1 && dim <= 3, "the MI355X hot path is built for hexahedral, quadrilateral and segment tensor-lattice meshes");
       const int ne = pfes.GetNE();
-      const int nc = 1 << dim, nf = 2 * dim, nst = dim == 3 ? 27 : 9; // corners, faces, stencil entries per element
+      const int nc = 1 << dim, nf = 2 * dim, nst = dim == 3 ? 27 : (dim == 2 ? 9 : 3); // corners, faces, stencil entries per element
       const int n_ghost = (int)ghost_vertices.size() / nc;
-      MFEM_VERIFY(dim == 3 || n_ghost == 0, "dim = 2 runs on one rank");
+      MFEM_VERIFY(dim == 3 || n_ghost == 0, "dim = 1 and dim = 2 run on one rank");
 
       // E-vectors of the nodes: [ne][dim][3^dim], node a = ax + 3 (ay + 3 az)
       const FiniteElementSpace &nfes = *x0.FESpace();
@@ -69,9 +71,34 @@ struct RMHContext
       for (size_t i = 0; i < ghost_vertices.size(); i++) { ev[(size_t)ne * nc + i] = ghost_vertices[i]; }
       // neighbour tables for any element numbering (replaces the H1 bounds space of DofInfo, remhos_tools.cpp:355-379)
       std::vector<int> face_nbr((size_t)ne * nf), stencil((size_t)ne * nst);
-      MFEM_VERIFY((dim == 3 ? rmh_build_tables(ne, ne + n_ghost, ev.data(), face_nbr.data(), stencil.data())
-                            : rmh_build_tables_2d(ne, ne, ev.data(), face_nbr.data(), stencil.data())) == 0,
-                  "rmh_build_tables: the mesh is not an aligned tensor lattice");
+      if (dim == 1)
+      {
+         // segments: the left neighbour is the element whose right vertex is this element's left vertex, and vice versa
+         int nv = 0;
+         for (int id : ev) { nv = std::max(nv, id + 1); }
+         std::vector<int> left_of(nv, -1), right_of(nv, -1); // element that has the vertex as its right / left end
+         for (int e = 0; e < ne; e++)
+         {
+            // every vertex is the left end of at most one segment and the right end of at most one: a segment whose vertex order
+            // is flipped against its neighbour's would otherwise lose that neighbour and the seam would pass for a domain boundary
+            MFEM_VERIFY(ev[2 * e] != ev[2 * e + 1] && right_of[ev[2 * e]] < 0 && left_of[ev[2 * e + 1]] < 0,
+                        "dim = 1: the segments are not oriented alike (not an aligned lattice)");
+            right_of[ev[2 * e]] = e;
+            left_of[ev[2 * e + 1]] = e;
+         }
+         for (int e = 0; e < ne; e++)
+         {
+            face_nbr[2 * e] = stencil[3 * e] = left_of[ev[2 * e]];
+            stencil[3 * e + 1] = e;
+            face_nbr[2 * e + 1] = stencil[3 * e + 2] = right_of[ev[2 * e + 1]];
+         }
+      }
+      else
+      {
+         MFEM_VERIFY((dim == 3 ? rmh_build_tables(ne, ne + n_ghost, ev.data(), face_nbr.data(), stencil.data())
+                               : rmh_build_tables_2d(ne, ne, ev.data(), face_nbr.data(), stencil.data())) == 0,
+                     "rmh_build_tables: the mesh is not an aligned tensor lattice");
+      }
 
       rmh_layout L = {};
       L.dim = dim;

@@ -45,7 +45,7 @@ typedef enum {
  * elements, plus edge/vertex neighbours for the bounds stencil). */
 typedef struct {
    int dim;          /* 3: hexahedra (the whole API).  2: quadrilaterals -- HO solver + granular limiter sequence *
-                      *    (see "dim = 2" below)                                                */
+                      *    (see "dim = 2" below).  1: segments (see "dim = 1" below)            */
    int order;        /* polynomial order p of the Bernstein DG space (-o, remhos.cpp:261)   */
    int mesh_order;   /* order of the nodal mesh (-mo, remhos.cpp:222); 2                    */
    int exec_mode;    /* 0 transport, 1 remap (remhos.cpp:437-440)                           */
@@ -83,6 +83,25 @@ typedef struct {
  * rmh_limit_fused, rmh_limit_fused_lo, rmh_stage_fused (the whole rank: HO kernel, RD solver for lo 3 / 4 and the fused limiter run
  * as a sequence inside the library; no tokens), the mass-rule / bounds-type / dt-control setters and getters, timers.  Everything
  * else (element ranges of a stage, the batch order, halo packing, exchange) returns RMH_ERR_INVALID for a 2-D context. */
+
+/* dim = 1 (segment lattices; remhos_amd/csrc/rmh_1d.hpp: one lane per element, one kernel per stage): the reference's 1-D regression
+ * runs (autotest/test.sh: data/periodic-segment.mesh, -p 0 -rs 3 -dt 0.001 -tf 1, -ho 2|3 -lo 3|4 -fct 2 [-pa]).  Layout: x0 / vel
+ * [ne][1][3] (mesh order 2, node a = ax), face_nbr [ne][2] (f = side, -1 on the domain boundary), `stencil27` = [ne][3] = (e - 1, e, e + 1)
+ * with the element itself in the middle (entries validated like the others), subcell_vel [ne][1][p + 1] or NULL, ne_ghost = 0; E-vectors
+ * carry p + 1 doubles per element; Q = p + 1 Gauss points (the rule of order 2p + 1: order = 2p + mo dim - 1, Q = order / 2 + 1, the
+ * formula that gives p + 2 in 2-D and p + 3 in 3-D); orders 1 to 6; both exec_modes, geometry from x0 + t vel at the time of the last
+ * rmh_setup(t).  Entry points, with the semantics and call-order rules of dim = 2: rmh_setup, rmh_ho_apply (also leaves the lumped
+ * mass and the element extrema), rmh_lumped_mass, rmh_compute_lumped_mass, rmh_lo_massavg, rmh_lo_rd, rmh_lo_rdsubcell (orders >= 2,
+ * the messages of the other dimensions), rmh_elem_minmax, rmh_bounds with rmh_set_bounds_type(0|1), rmh_fct_clipscale, rmh_limit_fused,
+ * rmh_limit_fused_lo, rmh_stage_fused with the y_out RK update (ONE kernel for the whole rank -- HO, LO of rmh_set_lo_type, extrema of the
+ * three stencil elements recomputed from u, bounds, clip + scale -- which also leaves the lumped mass and the element extrema of u; no
+ * tokens), rmh_check_violation, rmh_set_dt_control and the dt estimate, the timers.  Mass solve: Q = p + 1 makes the element mass matrix
+ * diagonal in the Gauss-Legendre nodal basis, so the (p + 1) x (p + 1) solve is exact and direct -- the semantics of -ho 3, with which
+ * -ho 2 and the -pa rule coincide to round-off.  rmh_set_mass_tol / rmh_set_mass_completion are accepted and have NO effect at dim = 1;
+ * rmh_last_cg_iters gives 0.  Everything else returns RMH_ERR_INVALID with a message that names the entry and "dim = 1":
+ * rmh_ho_neumann, rmh_lo_upwind, rmh_lo_upwind_prec, rmh_fct_projection, rmh_fct_fluxbased, rmh_mono_rd, the product entries
+ * (rmh_product_ratio, rmh_elem_minmax_masked, rmh_fct_product), element ranges of a stage, rmh_batch_order, rmh_halo_pack[_records],
+ * rmh_exchange_setup (the other exchange calls then find no plan, as at dim = 2). */
 
 /* Neighbour tables from mesh topology (host, no GPU): face_nbr and stencil27 of rmh_layout for ANY element numbering,
  * from the vertex ids of the elements -- what a binding has at hand (Mesh::GetElementVertices; periodic meshes: the

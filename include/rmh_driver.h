@@ -17,7 +17,9 @@ extern "C" {
 #endif
 
 typedef struct {
-   char mesh[32];     /* -m : "periodic-cube" | "cube01_hex" (data/ lattice meshes)             */
+   char mesh[32];     /* -m : "periodic-cube" | "cube01_hex" | "inline-quad" | "periodic-square" (dim = 2) | "periodic-segment" (dim = 1:
+                         problem 0, ho_type 2|3, lo_type 3|4|5, fct_type 0|2, ode_solver 3, fused 0|1, bounds_type, dt_control, verify_bounds on
+                         one block; pa = 1 is taken as 0 with the reference's warning; every other option is refused naming dim = 1) */
    int rs;            /* -rs                                                                  */
    int order;         /* -o                                                                   */
    int problem;       /* -p  (0 translation transport, 10 Taylor-Green remap, ...)            */
@@ -72,7 +74,8 @@ typedef struct {
 typedef struct {
    int order, exec_mode, ndof, ne_owned, ne_ghost, n_peers;
    int ne_halo;       /* owned elements [0, ne_halo) reach a ghost through their 27-stencil */
-   int dim;           /* 3: hexahedra; 2: quadrilaterals (inline-quad, periodic-square: one rank; arrays [ne][2][9], 4 faces, 3 x 3 stencil) */
+   int dim;           /* 3: hexahedra; 2: quadrilaterals (inline-quad, periodic-square: one rank; arrays [ne][2][9], 4 faces, 3 x 3 stencil);
+                         1: segments (periodic-segment: one rank; arrays [ne][1][3], 2 faces, stencil (e - 1, e, e + 1)) */
    long long ne_global;
    int n[3], lo[3], nl[3];
    double dt;

@@ -190,8 +190,10 @@ class Context:
         vel = np.ascontiguousarray(vel, dtype=np.float64)
         face_nbr = np.ascontiguousarray(face_nbr, dtype=np.int32)
         stencil27 = np.ascontiguousarray(stencil27, dtype=np.int32)
-        dim = x0.shape[1]  # 3: hexahedra; 2: quadrilaterals (nodes [ne][2][9], 4 faces, 3 x 3 stencil -- include/rmh.h)
-        assert dim in (2, 3) and x0.shape == (ne, dim, 3**dim) and vel.shape == (ne, dim, 3**dim)
+        # 3: hexahedra; 2: quadrilaterals (nodes [ne][2][9], 4 faces, 3 x 3 stencil); 1: segments (nodes [ne][1][3], 2 faces,
+        # stencil (e - 1, e, e + 1)) -- include/rmh.h
+        dim = x0.shape[1]
+        assert dim in (1, 2, 3) and x0.shape == (ne, dim, 3**dim) and vel.shape == (ne, dim, 3**dim)
         assert face_nbr.shape == (ne, 2 * dim) and stencil27.shape == (ne, 3**dim)
         L = RmhLayout()
         L.dim, L.order, L.mesh_order, L.exec_mode = dim, order, mesh_order, exec_mode

@@ -138,7 +138,7 @@ class Case:
         self.dt = info.dt
         self.bb_min, self.bb_max = list(info.bb_min), list(info.bb_max)
         ne, nd = self.ne_owned, self.ndof
-        dim = self.dim = info.dim  # 3, or 2 for the quadrilateral lattices (inline-quad, periodic-square)
+        dim = self.dim = info.dim  # 3; 2 for the quadrilateral lattices (inline-quad, periodic-square); 1 for periodic-segment
         self.x0 = _view(lib.rmhd_case_x0(h), (ne, dim, 3**dim), np.float64)
         self.vel = _view(lib.rmhd_case_vel(h), (ne, dim, 3**dim), np.float64)
         self.u0 = _view(lib.rmhd_case_u0(h), (ne, nd), np.float64)

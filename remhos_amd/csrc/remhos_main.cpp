@@ -3,6 +3,7 @@
 // lines (remhos.cpp:1423-1428, 1938-1952):
 //   remhos_amd -m periodic-cube -p 10 -rs 4 -o 3 -dt -1 -tf 0.5 -ms 20 -ho 3 -lo 5 -fct 2 -pa [-bt 1 -dtc 1]   (-fct 4: element FCT projection, -ho 1 / -lo 1 / -lo 2 / -fct 1: NeumannHOSolver / DiscreteUpwind / its preconditioned form / FluxBasedFCT; granular sequence;
 //   -mono 1: MonoRDSolver, the whole stage as one monolithic residual-distribution update -- -ho / -lo / -fct are then ignored)
+//   remhos_amd -m data/periodic-segment.mesh -p 0 -rs 3 -o 3 -dt 0.001 -tf 1 -ho 3 -lo 4 -fct 2    (dim = 1: -ho 2|3, -lo 3|4|5, -fct 2)
 #include "../../include/rmh_driver.h"
 
 #include <cstdio>

@@ -5,6 +5,7 @@
 #include "rmh_ho2.hpp"
 #include "rmh_stream.hpp"
 #include "rmh_2d.hpp"
+#include "rmh_1d.hpp"
 #include "rmh_efp.hpp"
 #include "rmh_upwind.hpp"
 #include "rmh_pdu.hpp"
@@ -312,6 +313,66 @@ int launch_stage_fused(rmh_ctx *c, const double *u, double dt, const double *x_b
 #define RMH_3D_ONLY(c, name)                                                                                              \
    if ((c)->dim != 3) { return fail(RMH_ERR_INVALID, name ": not available for dim = 2 (HO solver, granular limiter sequence and product remap only)"); }
 
+// entry points that a segment context (dim = 1, rmh_1d.hpp) does not have
+#define RMH_NOT_1D(c, name)                                                                                               \
+   if ((c)->dim == 1) { return fail(RMH_ERR_INVALID, name ": not available for dim = 1 (HO solver -ho 2|3, LO solvers -lo 3|4|5, clip + scale, one-kernel stage)"); }
+
+// dim = 1 (rmh_1d.hpp): nodes [ne][3], face_nbr [ne][2], the stencil (e - 1, e, e + 1) [ne][3]; one lane per element
+constexpr int SEG_NT = 64;
+inline int seg_grid(const rmh_ctx *c) { return (c->ne + SEG_NT - 1) / SEG_NT; }
+
+template <int P>
+int create_tables_1d(rmh_ctx *c)
+{
+   std::vector<double> tab = make_tables_q<P, P + 1>();
+   return upload(&c->d_tab, tab.data(), tab.size());
+}
+
+int create_device_state_1d(rmh_ctx *c, const rmh_layout *L)
+{
+   const size_t ne = c->ne;
+   int rc = 0;
+   if ((rc = upload(&c->d_x0, L->x0, ne * 3))) { return rc; }
+   if ((rc = upload(&c->d_vel, L->vel, ne * 3))) { return rc; }
+   if ((rc = upload(&c->d_nbr, L->face_nbr, ne * 2))) { return rc; }
+   if ((rc = upload(&c->d_st27, L->stencil27, ne * 3))) { return rc; }
+   if (L->subcell_vel && (rc = upload(&c->d_subvel, L->subcell_vel, ne * c->ndof))) { return rc; }
+   RMH_DISPATCH(c, rc = create_tables_1d<P>(c));
+   if (rc) { return rc; }
+   RMH_HIP(hipMalloc((void **)&c->d_m, ne * c->ndof * sizeof(double)));
+   RMH_HIP(hipMalloc((void **)&c->d_xe_min, ne * sizeof(double)));
+   RMH_HIP(hipMalloc((void **)&c->d_xe_max, ne * sizeof(double)));
+   RMH_HIP(hipMalloc((void **)&c->d_cg, sizeof(int))); // (stays 0: the mass solve of a segment is direct)
+   RMH_HIP(hipMemset(c->d_cg, 0, sizeof(int)));
+   return 0;
+}
+
+SegArgs seg_args(const rmh_ctx *c, double t, bool subcell)
+{
+   SegArgs a;
+   a.x0 = c->d_x0;
+   a.vel = c->d_vel;
+   a.face_nbr = c->d_nbr;
+   a.st3 = c->d_st27;
+   a.tab = c->d_tab;
+   a.subvel = subcell ? c->d_subvel : nullptr;
+   a.t = t;
+   a.move = c->exec_mode == 1 ? 1 : 0;
+   a.alpha = c->exec_mode == 1 ? 1.0 : -1.0; // remhos.cpp:648-657
+   a.upw = c->exec_mode == 1 ? 1.0 : -1.0;
+   a.ne = c->ne;
+   return a;
+}
+
+template <int P, int MODE>
+int launch_ho_1d(rmh_ctx *c, const double *u, double *du, double *m, double t, int rd_subcell)
+{
+   const SegArgs a = seg_args(c, t, MODE == 2 && rd_subcell);
+   hipLaunchKernelGGL((seg_ho_kernel<P, MODE>), dim3(seg_grid(c)), dim3(SEG_NT), 0, c->stream, a, u, du, m, c->d_xe_min, c->d_xe_max);
+   RMH_HIP(hipGetLastError());
+   return 0;
+}
+
 // dim = 2: nodes [ne][2][9], face_nbr [ne][4]; the caller's 3 x 3 element stencil [ne][9] becomes the middle layer of the
 // 27-entry table that the bounds kernels read (no neighbours along z)
 template <int P>
@@ -540,7 +601,8 @@ int lo_rd(rmh_ctx *c, const double *u, double *du_lo, int rd_subcell)
    extrema_dropped(c);
    return timed(c, 2, [&]() -> int {
       int rc = 0;
-      if (c->dim == 2) { RMH_DISPATCH(c, rc = (launch_ho_2d<P, 2>(c, u, du_lo, c->d_m, c->t, rd_subcell))); }
+      if (c->dim == 1) { RMH_DISPATCH(c, rc = (launch_ho_1d<P, 2>(c, u, du_lo, c->d_m, c->t, rd_subcell))); }
+      else if (c->dim == 2) { RMH_DISPATCH(c, rc = (launch_ho_2d<P, 2>(c, u, du_lo, c->d_m, c->t, rd_subcell))); }
       else { RMH_DISPATCH(c, rc = (launch_ho<P, 2>(c, u, du_lo, c->d_m, c->t, rd_subcell))); }
       if (!rc) { c->ho_done = true; } // lumped mass and element extrema are current
       return rc;
@@ -595,9 +657,10 @@ int rmh_create(const rmh_layout *L, rmh_ctx **out)
 {
    if (!L || !out) { return fail(RMH_ERR_INVALID, "null argument"); }
    *out = nullptr;
-   if (L->dim != 3 && L->dim != 2) { return fail(RMH_ERR_INVALID, "dim must be 3 (or 2: HO solver and granular limiter sequence)"); }
-   const int nf = 2 * L->dim, nst = L->dim == 3 ? 27 : 9;
+   if (L->dim != 3 && L->dim != 2 && L->dim != 1) { return fail(RMH_ERR_INVALID, "dim must be 3 (or 2: HO solver and granular limiter sequence; or 1: segments)"); }
+   const int nf = 2 * L->dim, nst = L->dim == 3 ? 27 : (L->dim == 2 ? 9 : 3);
    if (L->dim == 2 && L->ne_ghost != 0) { return fail(RMH_ERR_INVALID, "dim = 2: single rank (ne_ghost = 0)"); }
+   if (L->dim == 1 && L->ne_ghost != 0) { return fail(RMH_ERR_INVALID, "dim = 1: single rank (ne_ghost = 0)"); }
    if (L->order < 1 || L->order > 6) { return fail(RMH_ERR_INVALID, "order must be in 1..6"); }
    if (L->mesh_order != 2) { return fail(RMH_ERR_INVALID, "mesh_order must be 2"); }
    if (L->ne_owned <= 0 || L->ne_ghost < 0) { return fail(RMH_ERR_INVALID, "bad element counts"); }
@@ -634,7 +697,7 @@ int rmh_create(const rmh_layout *L, rmh_ctx **out)
    c->exec_mode = L->exec_mode;
    c->device = L->device;
    c->dim = L->dim;
-   c->ndof = (c->p + 1) * (c->p + 1) * (c->dim == 3 ? c->p + 1 : 1);
+   c->ndof = (c->p + 1) * (c->dim >= 2 ? c->p + 1 : 1) * (c->dim == 3 ? c->p + 1 : 1);
    c->gh_ustride = c->ndof;
    if (c->ng > 0)
    {
@@ -664,7 +727,7 @@ int rmh_create(const rmh_layout *L, rmh_ctx **out)
       if (const char *s = std::getenv("RMH_XCD_WEAVE")) { c->xcd_weave = std::min(4, std::max(0, std::atoi(s))); }
    }
    // every failure past this point releases the context and whatever it already owns
-   const int rc = c->dim == 3 ? create_device_state(c, L) : create_device_state_2d(c, L);
+   const int rc = c->dim == 3 ? create_device_state(c, L) : (c->dim == 2 ? create_device_state_2d(c, L) : create_device_state_1d(c, L));
    if (rc) { rmh_destroy(c); return rc; }
    *out = c;
    return RMH_OK;
@@ -695,6 +758,7 @@ int rmh_set_stream(rmh_ctx *c, void *s)
 int rmh_batch_order(rmh_ctx *c, int n_elements, int *layer_elements, int *batch_elements, int *chunk, int *weave)
 {
    if (!c || !layer_elements || !batch_elements || !chunk || !weave || n_elements < 0) { return fail(RMH_ERR_INVALID, "rmh_batch_order: bad argument"); }
+   RMH_NOT_1D(c, "rmh_batch_order");
    RMH_3D_ONLY(c, "rmh_batch_order");
    int nb = 1;
    RMH_DISPATCH(c, nb = stage_batch_elements<P>(c));
@@ -788,7 +852,8 @@ int rmh_ho_apply(rmh_ctx *c, const double *u, double *du)
    if (int rc = ghost_u_ready(c)) { return rc; }
    return timed(c, 0, [&]() -> int {
       int rc = 0;
-      if (c->dim == 2) { RMH_DISPATCH(c, rc = (launch_ho_2d<P, 0>(c, u, du, c->d_m, c->t, rd_subcell_of(c)))); }
+      if (c->dim == 1) { RMH_DISPATCH(c, rc = (launch_ho_1d<P, 0>(c, u, du, c->d_m, c->t, 0))); }
+      else if (c->dim == 2) { RMH_DISPATCH(c, rc = (launch_ho_2d<P, 0>(c, u, du, c->d_m, c->t, rd_subcell_of(c)))); }
       else { RMH_DISPATCH(c, rc = (launch_ho<P, 0>(c, u, du, c->d_m, c->t, rd_subcell_of(c)))); }
       if (rc) { return rc; }
       c->ho_done = true; // (once the launch is made, whatever becomes of the stopwatch)
@@ -804,6 +869,11 @@ int rmh_compute_lumped_mass(rmh_ctx *c, double t, double *m)
    if (!c || !m) { return fail(RMH_ERR_INVALID, "null argument"); }
    RMH_ENTER(c);
    int rc = 0;
+   if (c->dim == 1)
+   {
+      RMH_DISPATCH(c, rc = (launch_ho_1d<P, 4>(c, nullptr, nullptr, m, t, 0)));
+      return rc;
+   }
    if (c->dim == 2)
    {
       RMH_DISPATCH(c, rc = (launch_ho_2d<P, 4>(c, nullptr, nullptr, m, t, rd_subcell_of(c))));
@@ -822,6 +892,14 @@ int rmh_lo_massavg(rmh_ctx *c, const double *u, const double *du_ho, double dt, 
    RMH_ENTER(c);
    extrema_dropped(c);
    if (!c->ho_done) { return fail(RMH_ERR_STATE, "rmh_lo_massavg needs the lumped mass of rmh_ho_apply"); }
+   if (c->dim == 1)
+   {
+      return timed(c, 2, [&]() -> int {
+         RMH_DISPATCH(c, hipLaunchKernelGGL((seg_massavg_kernel<P>), dim3(seg_grid(c)), dim3(SEG_NT), 0, c->stream, u, du_ho,
+                                            (const double *)c->d_m, dt, du_lo, c->ne));
+         return 0;
+      });
+   }
    return timed(c, 2, [&]() -> int {
       RMH_DISPATCH_PD(c, hipLaunchKernelGGL((lo_massavg_kernel<P, DIM>), dim3(c->ne), dim3(KCfg<P, DIM>::NT), 0, c->stream, u, du_ho,
                                             (const double *)c->d_m, dt, du_lo));
@@ -850,6 +928,12 @@ int rmh_elem_minmax(rmh_ctx *c, const double *u, double *xe_min, double *xe_max)
 {
    if (!c || !u || !xe_min || !xe_max) { return fail(RMH_ERR_INVALID, "null argument"); }
    RMH_ENTER(c);
+   if (c->dim == 1)
+   {
+      RMH_DISPATCH(c, hipLaunchKernelGGL((seg_minmax_kernel<P>), dim3(seg_grid(c)), dim3(SEG_NT), 0, c->stream, u, xe_min, xe_max, c->ne));
+      RMH_HIP(hipGetLastError());
+      return RMH_OK;
+   }
    RMH_DISPATCH_PD(c, hipLaunchKernelGGL((elem_minmax_kernel<P, DIM>), dim3(SCfg<P, DIM>::grid(c->ne, SCfg<P, DIM>::U8)),
                                          dim3(SCfg<P, DIM>::NT), 0, c->stream, u, xe_min, xe_max, c->ne));
    RMH_HIP(hipGetLastError());
@@ -863,6 +947,13 @@ int rmh_bounds(rmh_ctx *c, const double *xe_min, const double *xe_max, double *u
    extrema_dropped(c);
    if (c->ng > 0 && (!c->gh_min || !c->gh_max)) { return fail(RMH_ERR_STATE, "ghost extrema not set"); }
    if (const char *why = ghosts_in_flight(c)) { return fail(RMH_ERR_STATE, why); }
+   if (c->dim == 1)
+   {
+      RMH_DISPATCH(c, hipLaunchKernelGGL((seg_bounds_kernel<P>), dim3(seg_grid(c)), dim3(SEG_NT), 0, c->stream, c->bounds_type,
+                                         (const int *)c->d_st27, xe_min, xe_max, u_min, u_max, c->ne));
+      RMH_HIP(hipGetLastError());
+      return RMH_OK;
+   }
    const int wide = (((uintptr_t)u_min | (uintptr_t)u_max) & 15) == 0; // 16-byte stores
    RMH_DISPATCH_PD(c, hipLaunchKernelGGL((bounds_kernel<P, DIM>), dim3(SCfg<P, DIM>::grid(c->ne, SCfg<P, DIM>::UB)), dim3(SCfg<P, DIM>::NT), 0,
                                          c->stream, c->bounds_type, (const int *)c->d_st27, c->ne, xe_min, xe_max, c->gh_min, c->gh_max,
@@ -877,6 +968,14 @@ int rmh_fct_clipscale(rmh_ctx *c, const double *u, const double *m, const double
    if (int rc = check_limiter_args(c, u, m, du_ho, du_lo, u_min, u_max, du)) { return rc; }
    RMH_ENTER(c);
    extrema_dropped(c);
+   if (c->dim == 1)
+   {
+      return timed(c, 3, [&]() -> int {
+         RMH_DISPATCH(c, hipLaunchKernelGGL((seg_clipscale_kernel<P>), dim3(seg_grid(c)), dim3(SEG_NT), 0, c->stream, u, m, du_ho, du_lo,
+                                            u_min, u_max, dt, du, c->ne));
+         return 0;
+      });
+   }
    return timed(c, 3, [&]() -> int {
       RMH_DISPATCH_PD(c, hipLaunchKernelGGL((fct_clipscale_kernel<P, DIM>), dim3(c->ne), dim3(KCfg<P, DIM>::NT), 0, c->stream, u, m, du_ho,
                                             du_lo, u_min, u_max, dt, du));
@@ -888,6 +987,7 @@ int rmh_fct_projection(rmh_ctx *c, const double *u, const double *m, const doubl
                        const double *u_min, const double *u_max, double dt, double *du)
 {
    if (int rc = check_limiter_args(c, u, m, du_ho, du_lo, u_min, u_max, du)) { return rc; }
+   RMH_NOT_1D(c, "rmh_fct_projection (-fct 4)");
    if (!(dt > 0.0)) { return fail(RMH_ERR_INVALID, "dt must be positive"); }
    RMH_ENTER(c);
    extrema_dropped(c);
@@ -903,6 +1003,7 @@ int rmh_fct_projection(rmh_ctx *c, const double *u, const double *m, const doubl
 int rmh_lo_upwind(rmh_ctx *c, const double *u, double *du_lo)
 {
    if (!c || !u || !du_lo) { return fail(RMH_ERR_INVALID, "null argument"); }
+   RMH_NOT_1D(c, "rmh_lo_upwind (-lo 1)");
    if (int rc = ghost_u_ready(c)) { return rc; }
    RMH_ENTER(c);
    extrema_dropped(c);
@@ -918,6 +1019,7 @@ int rmh_lo_upwind(rmh_ctx *c, const double *u, double *du_lo)
 int rmh_lo_upwind_prec(rmh_ctx *c, const double *u, double *du_lo)
 {
    if (!c || !u || !du_lo) { return fail(RMH_ERR_INVALID, "null argument"); }
+   RMH_NOT_1D(c, "rmh_lo_upwind_prec (-lo 2)");
    if (c->dim == 3 && c->p >= 4)
    {
       return fail(RMH_ERR_INVALID, "rmh_lo_upwind_prec (-lo 2): order " + std::to_string(c->p) +
@@ -947,6 +1049,7 @@ int rmh_lo_upwind_prec(rmh_ctx *c, const double *u, double *du_lo)
 int rmh_mono_rd(rmh_ctx *c, const double *u, const double *xi_min, const double *xi_max, const double *scale, int mass_lim, double *du)
 {
    if (!c || !u || !xi_min || !xi_max || !scale || !du) { return fail(RMH_ERR_INVALID, "null argument"); }
+   RMH_NOT_1D(c, "rmh_mono_rd (-mono 1)");
    if (c->ng > 0)
    {
       return fail(RMH_ERR_INVALID, "rmh_mono_rd (-mono 1): contexts with ghost elements are not supported (the solver runs on one block)");
@@ -1003,6 +1106,7 @@ int rmh_mono_passes(rmh_ctx *c, int *passes)
 int rmh_ho_neumann(rmh_ctx *c, const double *u, double *du)
 {
    if (!c || !u || !du) { return fail(RMH_ERR_INVALID, "null argument"); }
+   RMH_NOT_1D(c, "rmh_ho_neumann (-ho 1)");
    if (c->ng > 0)
    {
       return fail(RMH_ERR_INVALID, "rmh_ho_neumann (-ho 1): contexts with ghost elements are not supported (the global residual norm would need a reduction over the ranks: the solver runs on one rank)");
@@ -1058,6 +1162,7 @@ int rmh_fct_fluxbased(rmh_ctx *c, const double *u, const double *m, const double
                       const double *u_min, const double *u_max, double dt, double *du)
 {
    if (int rc = check_limiter_args(c, u, m, du_ho, du_lo, u_min, u_max, du)) { return rc; }
+   RMH_NOT_1D(c, "rmh_fct_fluxbased (-fct 1)");
    if (!(dt > 0.0)) { return fail(RMH_ERR_INVALID, "dt must be positive"); }
    if (c->ng > 0)
    {
@@ -1077,6 +1182,7 @@ int rmh_product_ratio(rmh_ctx *c, const double *us, const double *u, double *s, 
                       unsigned char *active_dofs)
 {
    if (!c || !u || !active_el || !active_dofs || ((us != nullptr) != (s != nullptr))) { return fail(RMH_ERR_INVALID, "null argument"); }
+   RMH_NOT_1D(c, "rmh_product_ratio (-ps)");
    RMH_ENTER(c);
    extrema_dropped(c);
    if (c->dim == 2)
@@ -1097,6 +1203,7 @@ int rmh_elem_minmax_masked(rmh_ctx *c, const double *u, const unsigned char *act
                            double *xe_min, double *xe_max)
 {
    if (!c || !u || !active_el || !active_dofs || !xe_min || !xe_max) { return fail(RMH_ERR_INVALID, "null argument"); }
+   RMH_NOT_1D(c, "rmh_elem_minmax_masked (-ps)");
    RMH_ENTER(c);
    if (c->dim == 2)
    {
@@ -1120,6 +1227,7 @@ int rmh_fct_product(rmh_ctx *c, const double *us, const double *m, const double 
    {
       return fail(RMH_ERR_INVALID, "null argument");
    }
+   RMH_NOT_1D(c, "rmh_fct_product (-ps)");
    if (!(dt > 0.0)) { return fail(RMH_ERR_INVALID, "dt must be positive"); }
    RMH_ENTER(c);
    extrema_dropped(c);
@@ -1148,6 +1256,30 @@ static int limit_fused_impl(rmh_ctx *c, const double *u, const double *du_ho, co
    extrema_dropped(c);
    if (c->ng > 0 && (!c->gh_min || !c->gh_max)) { return fail(RMH_ERR_STATE, "ghost extrema not set"); }
    if (const char *why = ghosts_not_ready(c, 0)) { return fail(RMH_ERR_STATE, why); }
+   if (c->dim == 1)
+   {
+      const SegArgs sa = seg_args(c, c->t, false);
+      SegStageArgs ss = {};
+      ss.u = u;
+      ss.du_ho = du_ho;
+      ss.du_lo = du_lo;
+      ss.xe_min = c->d_xe_min;
+      ss.xe_max = c->d_xe_max;
+      ss.m = c->d_m;
+      ss.bounds_type = c->bounds_type;
+      ss.dt = dt;
+      ss.dt_est = c->dt_control ? c->d_dt_est : nullptr;
+      ss.du = du;
+      ss.x_base = x_base;
+      ss.a = a;
+      ss.b = b;
+      ss.dt_rk = dt_rk;
+      ss.y_out = y_out;
+      return timed(c, 3, [&]() -> int {
+         RMH_DISPATCH(c, hipLaunchKernelGGL((seg_limit_kernel<P>), dim3(seg_grid(c)), dim3(SEG_NT), 0, c->stream, sa, ss));
+         return 0;
+      });
+   }
    LimitArgs la;
    la.u = u;
    la.du_ho = du_ho;
@@ -1198,6 +1330,36 @@ int rmh_stage_fused_chain(rmh_ctx *c, const double *u, double dt, const double *
    RMH_ENTER(c);
    if (!(dt > 0.0)) { return fail(RMH_ERR_INVALID, "dt must be positive"); }
    if (y_out == u || du == u) { return fail(RMH_ERR_INVALID, "rmh_stage_fused: the output must not alias u"); }
+   if (c->dim == 1)
+   {
+      // dim = 1: the whole stage of the whole rank in ONE kernel (rmh_1d.hpp); it also leaves the lumped mass and the element
+      // extrema of u, like rmh_ho_apply; no tokens
+      if (e_begin != 0 || e_end != c->ne || !finish) { return fail(RMH_ERR_INVALID, "rmh_stage_fused_range: dim = 1 runs the whole rank in one call"); }
+      if ((c->lo_type == 3 || c->lo_type == 4) && c->p < 2) { return fail(RMH_ERR_STATE, "rmh_stage_fused with lo 3 / 4 needs order >= 2"); }
+      if (c->lo_type == 4 && !c->d_subvel) { return fail(RMH_ERR_STATE, "rmh_stage_fused with lo 4 needs rmh_layout.subcell_vel"); }
+      const SegArgs sa = seg_args(c, c->t, c->lo_type == 4);
+      SegStageArgs ss = {};
+      ss.u = u;
+      ss.m = c->d_m;
+      ss.xe_min_out = c->d_xe_min;
+      ss.xe_max_out = c->d_xe_max;
+      ss.lo_type = c->lo_type;
+      ss.bounds_type = c->bounds_type;
+      ss.dt = dt;
+      ss.dt_est = c->dt_control ? c->d_dt_est : nullptr;
+      ss.du = du;
+      ss.x_base = x_base;
+      ss.a = a;
+      ss.b = b;
+      ss.dt_rk = dt_rk;
+      ss.y_out = y_out;
+      extrema_dropped(c);
+      return timed(c, 0, [&]() -> int {
+         RMH_DISPATCH(c, hipLaunchKernelGGL((seg_stage_kernel<P>), dim3(seg_grid(c)), dim3(SEG_NT), 0, c->stream, sa, ss));
+         c->ho_done = true; // (lumped mass and element extrema of u are current)
+         return 0;
+      });
+   }
    if (c->dim == 2)
    {
       // dim = 2: the whole stage as a sequence inside the library -- HO kernel (lumped mass, element extrema), the RD solver
@@ -1288,6 +1450,7 @@ int rmh_halo_pack(rmh_ctx *c, const double *u, const int *send_elems, int nsend,
                   double *out_max)
 {
    if (!c || !u || (nsend > 0 && (!send_elems || !rows || !out_min || !out_max))) { return fail(RMH_ERR_INVALID, "null argument"); }
+   RMH_NOT_1D(c, "rmh_halo_pack");
    RMH_3D_ONLY(c, "rmh_halo_pack");
    RMH_ENTER(c);
    if (nsend <= 0) { return RMH_OK; }
@@ -1300,6 +1463,7 @@ int rmh_halo_pack(rmh_ctx *c, const double *u, const int *send_elems, int nsend,
 int rmh_halo_pack_records(rmh_ctx *c, const double *u, const int *send_elems, int nsend, double *rec)
 {
    if (!c || !u || (nsend > 0 && (!send_elems || !rec))) { return fail(RMH_ERR_INVALID, "null argument"); }
+   RMH_NOT_1D(c, "rmh_halo_pack_records");
    RMH_3D_ONLY(c, "rmh_halo_pack_records");
    RMH_ENTER(c);
    if (nsend <= 0) { return RMH_OK; }

@@ -35,7 +35,8 @@ struct Exchange; // rmh_comm.hpp
 
 struct rmh_ctx
 {
-   int dim = 3; // 3: hexahedra (the whole API); 2: quadrilaterals (HO solver + the granular limiter sequence, rmh_2d.hpp)
+   int dim = 3; // 3: hexahedra (the whole API); 2: quadrilaterals (HO solver + the granular limiter sequence, rmh_2d.hpp);
+                // 1: segments (rmh_1d.hpp; d_st27 then holds the stencil (e - 1, e, e + 1) [ne][3])
    int p = 0, ne = 0, ng = 0, exec_mode = 0, device = 0;
    int ndof = 0;
    hipStream_t stream = nullptr;

@@ -325,6 +325,27 @@ static int check_fct_type(const rmhd_config *cfg, bool partitioned)
    return 0;
 }
 
+// dim = 1 (-m data/periodic-segment.mesh): what a segment run takes -- -ho 2|3, -lo 3|4|5, -fct 2, -s 3, one block.  Every
+// other option is refused here, before a device context exists (0 on success, else the message is in g_driver_error)
+static bool is_segment_mesh(const rmhd_config *cfg) { return std::strncmp(cfg->mesh, "periodic-segment", sizeof(cfg->mesh)) == 0; }
+static int check_dim1(const rmhd_config *cfg, bool partitioned)
+{
+   const char *why = nullptr;
+   const int ode = cfg->ode_solver, lo = cfg->lo_type, fct = cfg->fct_type;
+   if (cfg->ps) { why = "ps (-ps): product remap"; }
+   else if (ode != 0 && ode != 3) { why = "ode_solver (-s 11|12|13): the IDP solvers"; }
+   else if (cfg->ho_type == 1) { why = "ho_type 1 (-ho 1): the Neumann HO solver"; }
+   else if (lo == 1 || lo == 2) { why = "lo_type 1|2 (-lo 1|2): the DiscreteUpwind LO solvers"; }
+   else if (fct == 1 || fct == 4) { why = "fct_type 1|4 (-fct 1|4): the flux-based and element-projection FCT solvers"; }
+   else if (cfg->mono_type) { why = "mono_type (-mono): the monolithic RD solver"; }
+   else if (partitioned || cfg->px > 1 || cfg->py > 1 || cfg->pz > 1 || cfg->rank != 0) { why = "partitions (px, py, pz, rank): box-partitioned runs"; }
+   else if (cfg->self_wrap) { why = "self_wrap: the self-wrapped halo"; }
+   else if (cfg->save) { why = "save (-save): the MFEM mesh / field writer"; }
+   if (!why) { return 0; }
+   g_driver_error = std::string(why) + " is not available for dim = 1 (periodic-segment: -ho 2|3, -lo 3|4|5, -fct 2, -s 3, one block)";
+   return -1;
+}
+
 // remhos.cpp:1557-1594
 static void report_violation(const rmh_violation &v, const std::string &info)
 {
@@ -668,6 +689,20 @@ extern "C" int rmhd_run_rank(const rmhd_config *cfg, const char *comm_id_file, i
 {
    if (!cfg || !res) { g_driver_error = "null argument"; return -1; }
    std::memset(res, 0, sizeof(*res));
+   rmhd_config seg_cfg;
+   if (is_segment_mesh(cfg))
+   {
+      if (check_dim1(cfg, false) != 0) { return -1; }
+      if (cfg->pa)
+      {
+         // remhos.cpp:474-480; the element mass solve of a segment is exact either way (rmh_1d.hpp)
+         std::printf("Disabling PA / FA for 1D.\n");
+         std::fflush(stdout);
+         seg_cfg = *cfg;
+         seg_cfg.pa = 0;
+         cfg = &seg_cfg;
+      }
+   }
    if (check_mono_type(cfg, false) != 0) { return -1; }
    rmhd_config mono_cfg;
    if (cfg->mono_type)
@@ -1233,6 +1268,7 @@ extern "C" int rmhd_run_partitioned(const rmhd_config *cfg, const char *comm_id_
    CaseConfig cc0 = to_config(*cfg);
    const int nranks = cc0.px * cc0.py * cc0.pz;
    const bool rccl = comm_id_file && comm_id_file[0];
+   if (is_segment_mesh(cfg) && check_dim1(cfg, true) != 0) { return -1; }
    if (check_mono_type(cfg, true) != 0) { return -1; }
    if (check_fct_type(cfg, true) != 0) { return -1; }
    if (!cfg->fused) { g_driver_error = "rmhd_run_partitioned runs the one-kernel stage (fused = 1)"; return -1; }

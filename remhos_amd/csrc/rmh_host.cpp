@@ -278,8 +278,10 @@ double u0_function_2d(int problem, const double *bb_min, const double *bb_max, c
 // The problem ids whose velocity field AND initial condition are implemented above (remhos.cpp:2001-2355 defines more:
 // 2, 3, 6, 7 and 11 have no branch here).  An id outside the set used to run silently with v = 0 or u0 = 0 -- and with
 // -dt -1 a CFL step of 0.25 h / 1e-7; now it is an error of the case builder.
-static std::string check_problem(int problem)
+static std::string check_problem(int problem, int dim = 3)
 {
+   // dim = 1: the translation only -- the other velocity fields of remhos.cpp:2001-2120 need a second coordinate
+   if (dim == 1 && problem != 0) { return "problem " + std::to_string(problem) + " is not implemented for dim = 1 (problem 0 only)"; }
    const int pv = problem % 20, pu = problem % 10;
    const bool vel_ok = pv == 0 || pv == 1 || pv == 2 || pv == 4 || pv == 5 || pv == 10 || (pv >= 12 && pv <= 17);
    const bool u0_ok = pu == 0 || pu == 1 || pu == 4 || pu == 5;
@@ -451,8 +453,78 @@ static std::string build_case_2d(const CaseConfig &cfg, CaseData &out)
    return "";
 }
 
+// The reference's 1-D mesh on ONE rank: data/periodic-segment.mesh (4 segments on [0,1], periodic), problem 0 -- what
+// autotest/test.sh runs with -p 0 -rs 3 -dt 0.001 -tf 1.  v = 1 (remhos.cpp:2022), u0 = exp(-40 (X - 0.5)^2) on the
+// bounding-box map (remhos.cpp:2223), sampled at the closed-uniform points.  Layout: x0 / vel [ne][1][3], face_nbr [ne][2],
+// stencil27 = (e - 1, e, e + 1) [ne][3], subcell_vel [ne][1][p + 1].
+static std::string build_case_1d(const CaseConfig &cfg, CaseData &out)
+{
+   if (cfg.order < 1 || cfg.order > 6) { return "order must be in 1..6"; }
+   if (cfg.px != 1 || cfg.py != 1 || cfg.pz != 1 || cfg.rank != 0) { return "partitions: dim = 1 runs on one rank"; }
+   if (cfg.self_wrap != 0) { return "self_wrap: dim = 1 runs on one rank without a halo"; }
+   if (cfg.rs_extra[0] || cfg.rs_extra[1] || cfg.rs_extra[2]) { return "dim = 1: no rs_extra"; }
+   if (cfg.lo_type != 3 && cfg.lo_type != 4 && cfg.lo_type != 5) { return "lo_type " + std::to_string(cfg.lo_type) + " is not available for dim = 1 (3, 4 or 5)"; }
+   if (const std::string e = check_problem(cfg.problem, 1); !e.empty()) { return e; }
+   if (cfg.rs < 0 || cfg.rs > 24) { return "bad rs"; }
+   const std::vector<double> verts = refine({0.0, 0.25, 0.5, 0.75, 1.0}, cfg.rs);
+   const int N = (int)verts.size() - 1, p = cfg.order, D = p + 1;
+   out = CaseData();
+   out.dim = 1;
+   out.order = p;
+   out.exec_mode = 0;
+   out.ndof = D;
+   out.periodic = true;
+   out.ne_global = N;
+   out.ne_owned = N;
+   for (int d = 0; d < 3; d++)
+   {
+      out.n[d] = d < 1 ? N : 1;
+      out.lo[d] = 0;
+      out.nl[d] = out.n[d];
+      out.bb_min[d] = d < 1 ? verts.front() : 0.0;
+      out.bb_max[d] = d < 1 ? verts.back() : 0.0;
+   }
+   // time step (remhos.cpp:538-553): 0.25 |det J(center)| / |v(center)|, det J(center) = x_2 - x_0 of the Q2 segment
+   double dt = cfg.dt;
+   if (dt < 0.0)
+   {
+      dt = INFINITY;
+      for (int e = 0; e < N; e++) { dt = std::fmin(dt, 0.25 * std::fabs(verts[e + 1] - verts[e]) / std::sqrt(1.0 + 1e-14)); }
+   }
+   out.dt = dt;
+   out.x0.resize((size_t)N * 3);
+   out.vel.assign((size_t)N * 3, 1.0);
+   out.u0.resize((size_t)N * D);
+   out.s0.assign((size_t)N * D, 0.0); // (no product field at dim = 1)
+   if (cfg.lo_type == 4) { out.subcell_vel.assign((size_t)N * D, 1.0); } // transport: the advection velocity at the sub-mesh nodes
+   out.owned_gid.resize(N);
+   out.stencil27.resize((size_t)N * 3);
+   out.face_nbr.resize((size_t)N * 2);
+   for (int e = 0; e < N; e++)
+   {
+      out.owned_gid[e] = e;
+      double *X = &out.x0[(size_t)e * 3];
+      X[0] = verts[e];
+      X[1] = 0.5 * verts[e] + 0.5 * verts[e + 1];
+      X[2] = verts[e + 1];
+      for (int i = 0; i < D; i++)
+      {
+         double L[3];
+         lag2((double)i / p, L);
+         const double x[3] = {L[0] * X[0] + L[1] * X[1] + L[2] * X[2], 0.0, 0.0};
+         const double Xr = 2 * (x[0] - (out.bb_min[0] + out.bb_max[0]) * 0.5) / (out.bb_max[0] - out.bb_min[0]);
+         out.u0[(size_t)e * D + i] = std::exp(-40. * (Xr - 0.5) * (Xr - 0.5)); // remhos.cpp:2223, sampled as at :878-884
+      }
+      out.stencil27[(size_t)e * 3 + 0] = out.face_nbr[(size_t)e * 2 + 0] = (e + N - 1) % N;
+      out.stencil27[(size_t)e * 3 + 1] = e;
+      out.stencil27[(size_t)e * 3 + 2] = out.face_nbr[(size_t)e * 2 + 1] = (e + 1) % N;
+   }
+   return "";
+}
+
 std::string build_case(const CaseConfig &cfg, CaseData &out)
 {
+   if (cfg.mesh == "periodic-segment") { return build_case_1d(cfg, out); }
    if (cfg.mesh == "inline-quad" || cfg.mesh == "periodic-square") { return build_case_2d(cfg, out); }
    MeshDef md;
    if (!lookup_mesh(cfg.mesh, md)) { return "unknown lattice mesh '" + cfg.mesh + "' (periodic-cube, cube01_hex)"; }
@@ -953,6 +1025,35 @@ std::string lp_error_sums(const CaseData &d, int problem, double t_exact, const 
       if (d.dim == 2) { velocity_function_2d(problem, d.bb_min, d.bb_max, x0, vel); }
       else { velocity_function(problem, d.bb_min, d.bb_max, x0, vel); } // (a constant)
    }
+   if (d.dim == 1)
+   {
+      // segments: nodes [ne][1][3], p + 1 Bernstein coefficients per element; problem 0 only (v = 1)
+      if (prob != 0) { return "dim = 1: the exact field is defined for problem 0"; }
+      long double a1 = 0.0L, a2 = 0.0L;
+      const double len = d.bb_max[0] - d.bb_min[0];
+      for (int e = 0; e < d.ne_owned; e++)
+      {
+         const double *X = &d.x0[(size_t)e * 3];
+         const double *ue = u + (size_t)e * d.ndof;
+         for (int q = 0; q < nq; q++)
+         {
+            double x = 0.0, J = 0.0, uh = 0.0;
+            for (int a = 0; a < 3; a++) { x += L[3 * q + a] * X[a]; J += dL[3 * q + a] * X[a]; }
+            for (int i = 0; i < D; i++) { uh += B[(size_t)q * D + i] * ue[i]; }
+            double r = std::fmod(x - 1.0 * t_exact - d.bb_min[0], len);
+            if (r < 0.0) { r += len; }
+            const double Xr = 2 * (d.bb_min[0] + r - (d.bb_min[0] + d.bb_max[0]) * 0.5) / len;
+            const double ex = std::fabs(uh - std::exp(-40. * (Xr - 0.5) * (Xr - 0.5)));
+            const double w = wq[q] * std::fabs(J);
+            a1 += w * ex;
+            a2 += w * ex * ex;
+            err[2] = std::fmax(err[2], ex);
+         }
+      }
+      err[0] = (double)a1;
+      err[1] = (double)a2;
+      return "";
+   }
    if (d.dim == 2)
    {
       // the same sums on quadrilaterals: nodes [ne][2][9], (p + 1)^2 Bernstein coefficients per element
@@ -1098,7 +1199,7 @@ std::string lp_error_sums(const CaseData &d, int problem, double t_exact, const 
 std::string save_mfem(const CaseData &d, double t, const double *u, const char *mesh_path, const char *gf_path)
 {
    if (!mesh_path) { return "null mesh path"; }
-   if (d.dim != 3) { return "-save writes the 3-D meshes"; }
+   if (d.dim != 3) { return "-save writes the 3-D meshes (not available for dim = " + std::to_string(d.dim) + ")"; }
    if ((long long)d.ne_owned != d.ne_global)
    {
       return "rmhd_case_save writes the mesh of a single-rank case (PrintAsOne / SaveAsOne)";

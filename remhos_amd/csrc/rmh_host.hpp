@@ -40,7 +40,8 @@ struct Peer
 
 struct CaseData
 {
-   int dim = 3; // 3: hexahedra; 2: quadrilaterals (single rank: x0 / vel [ne][2][9], face_nbr [ne][4], stencil27 = 3 x 3 [ne][9])
+   int dim = 3; // 3: hexahedra; 2: quadrilaterals (single rank: x0 / vel [ne][2][9], face_nbr [ne][4], stencil27 = 3 x 3 [ne][9]);
+                // 1: segments (single rank: x0 / vel [ne][1][3], face_nbr [ne][2], stencil27 = (e - 1, e, e + 1) [ne][3])
    int order = 0, exec_mode = 0, ndof = 0;
    int ne_owned = 0, ne_ghost = 0;
    int ne_halo = 0;        // owned elements [0, ne_halo) have a ghost in their 27-stencil (ordered first)
