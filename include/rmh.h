@@ -82,7 +82,18 @@ typedef struct {
  * rmh_product_ratio, rmh_elem_minmax_masked, rmh_fct_product (remhos_amd/csrc/rmh_product2d.hpp: a wavefront per element), rmh_check_violation,
  * rmh_limit_fused, rmh_limit_fused_lo, rmh_stage_fused (the whole rank: HO kernel, RD solver for lo 3 / 4 and the fused limiter run
  * as a sequence inside the library; no tokens), the mass-rule / bounds-type / dt-control setters and getters, timers.  Everything
- * else (element ranges of a stage, the batch order, halo packing, exchange) returns RMH_ERR_INVALID for a 2-D context. */
+ * else (element ranges of a stage, the batch order, halo packing, exchange) returns RMH_ERR_INVALID for a 2-D context.
+ *
+ * dim = 2, unstructured (any conforming quadrilateral mesh: vertices of valence 3, 5, 6 ..., neighbours whose reference axes are
+ * turned against the element's; the reference's data/star-q2.mesh and data/periodic-hexagon.mesh): the same layout, with
+ * `stencil27` [ne][9] holding the element itself in the centre and -1 elsewhere (it is not read), and rmh_set_quad_topology called
+ * on the new context with the tables of rmh_build_tables_quad.  On such a context rmh_setup, rmh_ho_apply, rmh_lumped_mass,
+ * rmh_compute_lumped_mass, rmh_lo_massavg, rmh_lo_rd, rmh_lo_rdsubcell, rmh_elem_minmax, rmh_bounds (remhos_amd/csrc/rmh_bounds2d.hpp),
+ * rmh_fct_clipscale, rmh_check_violation, the setters, getters and timers work as on a lattice; the element-local
+ * rmh_fct_projection and product entries read no neighbour table and are not refused, but no test runs them on such a context
+ * (the driver refuses -fct 4 and -ps on a mesh file).  The entries that read the neighbour tables with the lattice rule -- rmh_limit_fused,
+ * rmh_limit_fused_lo, rmh_stage_fused*, rmh_ho_neumann, rmh_lo_upwind, rmh_lo_upwind_prec, rmh_fct_fluxbased, rmh_mono_rd -- return
+ * RMH_ERR_INVALID with a message that names the entry and "unstructured". */
 
 /* dim = 1 (segment lattices; remhos_amd/csrc/rmh_1d.hpp: one lane per element, one kernel per stage): the reference's 1-D regression
  * runs (autotest/test.sh: data/periodic-segment.mesh, -p 0 -rs 3 -dt 0.001 -tf 1, -ho 2|3 -lo 3|4 -fct 2 [-pa]).  Layout: x0 / vel
@@ -119,6 +130,28 @@ int rmh_build_tables(int ne_owned, int ne_total, const int *elem_vertices, int *
 /* The same for quadrilaterals (dim = 2): elem_vertices[ne_total][4], corner k = kx + 2 ky (MFEM's quadrilateral order 0..3 maps
  * to {0, 1, 3, 2}); outputs face_nbr[ne_owned][4] (f = 2*c + side) and the 3 x 3 stencil [ne_owned][9]. */
 int rmh_build_tables_2d(int ne_owned, int ne_total, const int *elem_vertices, int *face_nbr, int *stencil9);
+/* The tables of an UNSTRUCTURED quadrilateral mesh (dim = 2, one rank; host, no GPU): any conforming mesh, whatever the valence
+ * of its vertices and however the neighbours' reference axes are turned.  elem_vertices[ne][4] as above (corner k = kx + 2 ky).
+ * Outputs (caller-allocated):
+ *   face_nbr[ne][4]   : f = 2 c + side -> the element across the face, -1 on the domain boundary;
+ *   face_code[ne][4]  : bits 0-1 the neighbour's local face g = 2 c' + side' of the shared edge, bit 2 `flip`: set when the
+ *                       neighbour's tangential parameter runs the other way along it (the faces are parametrised from corner
+ *                       (0, 2), (1, 3), (0, 1), (2, 3)[0] to [1]; flip = the first corners differ).  Between consistently
+ *                       oriented elements flip = (ccw(f) == ccw(g)), faces 1 and 2 being counter-clockwise; a lattice has
+ *                       g = f ^ 1, flip = 0.  0 where face_nbr is -1;
+ *   corner_ptr[4 ne + 1], corner_elems[corner_ptr[4 ne]] : CSR, row 4 e + k = the OTHER elements that contain the vertex of
+ *                       corner k of element e, ascending (the CG-node sharing of DofInfo::ComputeOverlapBounds,
+ *                       remhos_tools.cpp:449-494, at a vertex).  corner_elems may be NULL: only corner_ptr is filled, so that a
+ *                       caller learns the size first.
+ * RMH_ERR_INVALID (rmh_last_error of the host library: rmhd_last_error): an element that is its own neighbour, an edge shared
+ * by more than two elements or two edges between the same pair of vertices (a periodic mesh that is too coarse), a degenerate
+ * element. */
+int rmh_build_tables_quad(int ne, const int *elem_vertices, int *face_nbr, unsigned char *face_code, int *corner_ptr,
+                          int *corner_elems);
+/* Hands the tables above to a dim = 2 context (HOST arrays, copied and validated like those of rmh_create; ne_ghost = 0), once,
+ * before its first solve: rmh_ho_apply / rmh_lo_rd* then read the neighbour's face layer through face_code and rmh_bounds reads
+ * face_nbr and the CSR instead of the 3 x 3 stencil (see "dim = 2, unstructured" above). */
+int rmh_set_quad_topology(rmh_ctx *ctx, const unsigned char *face_code, const int *corner_ptr, const int *corner_elems);
 
 /* Creation / destruction.  Replaces the construction of LocalInverseHOSolver, MassBasedAvg /
  * PAResidualDistributionSubcell, ClipScaleSolver and DofInfo (remhos.cpp:730, 912-995,

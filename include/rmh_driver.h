@@ -69,6 +69,14 @@ typedef struct {
                          through RK3 SSP with no LimitMult (remhos.cpp:1687); ho_type, lo_type and fct_type are ignored like in the
                          reference.  rmhd_run / rmhd_run_state on one block, fused = 0, no -ps; -bt 0|1, -vb and -save apply;
                          dim = 3: order <= 3.  2 (ResDistMonoSubcell) and a smoothness indicator (-si) are refused.             */
+   char mesh_file[256]; /* -m with a path: when `mesh` is none of the built-in lattice names, the "MFEM mesh v1.0" file of an
+                         UNSTRUCTURED quadrilateral mesh (dimension 2, geometry 3; plain vertices, H1 "Quadratic" nodes or L2_T1_2D_P1
+                         nodes: the reference's data/star-q2.mesh and data/periodic-hexagon.mesh; counter-clockwise elements; -rs splits
+                         2 x 2).  Ignored for a built-in name.  Neither built in nor a readable file: "unknown lattice mesh".  A file mesh
+                         runs ho_type 2|3 (0), pa, lo_type 3|4|5, fct_type 2 (0), bounds_type, dt_control, verify_bounds, ode_solver 3 (0)
+                         on one block with fused = 0; fused = 1, ho_type 1, lo_type 1|2, fct_type 1|4, mono_type, ps, ode_solver
+                         11|12|13, partitions, self_wrap and save are refused before a device context exists, with a message that names
+                         the option and "unstructured"; no error norms are reported.                                               */
 } rmhd_config;
 
 typedef struct {
@@ -80,6 +88,9 @@ typedef struct {
    int n[3], lo[3], nl[3];
    double dt;
    double bb_min[3], bb_max[3];
+   int unstructured;   /* 1: dim = 2 from a mesh file (rmhd_config.mesh_file): n = nl = (ne, 1, 1), `stencil27` [ne][9] names the element
+                          itself only, and the tables of rmh_build_tables_quad are there (rmhd_case_face_code, _corner_ptr, _corner_elems) */
+   int n_corner_elems; /* entries of rmhd_case_corner_elems */
 } rmhd_case_info;
 
 typedef struct rmhd_case rmhd_case;
@@ -97,6 +108,11 @@ const double *rmhd_case_subcell_vel(const rmhd_case *c); /* [ne_owned][3][ndof] 
 const double *rmhd_case_mono_scale(rmhd_case *c);        /* [ne_owned] scale(e) of MonoRDSolver's constructor (remhos_mono.cpp:37-57), made on first use */
 const int *rmhd_case_face_nbr(const rmhd_case *c);       /* [ne_owned][6]  */
 const int *rmhd_case_stencil27(const rmhd_case *c);      /* [ne_owned][27] */
+/* unstructured cases only (NULL otherwise): the vertex ids of the elements and the tables rmh_set_quad_topology takes (include/rmh.h) */
+const int *rmhd_case_elem_vertices(const rmhd_case *c);          /* [ne_owned][4], corner k = kx + 2 ky */
+const unsigned char *rmhd_case_face_code(const rmhd_case *c);    /* [ne_owned][4] */
+const int *rmhd_case_corner_ptr(const rmhd_case *c);             /* [4 ne_owned + 1] */
+const int *rmhd_case_corner_elems(const rmhd_case *c);           /* [n_corner_elems] */
 const long long *rmhd_case_owned_gid(const rmhd_case *c);
 const long long *rmhd_case_ghost_gid(const rmhd_case *c);
 /* k-th neighbour rank of the halo exchange: owned elements it needs / ghost slots it fills */
@@ -108,6 +124,15 @@ int rmhd_case_peer(const rmhd_case *c, int k, int *rank, int *nsend, const int *
  * field as an MFEM GridFunction file (L2_T2_3D_P<order>, the positive basis of remhos.cpp:588-590).  Elements are
  * written in lattice order (global id).  Single-rank cases only (PrintAsOne / SaveAsOne).  0 on success. */
 int rmhd_case_save(const rmhd_case *c, double t, const double *u, const char *mesh_path, const char *gf_path);
+
+/* 1 if `name` is one of the lattice meshes the case builder has built in (any other name is read from rmhd_config.mesh_file) */
+int rmhd_is_builtin_mesh(const char *name);
+
+/* The error sums behind err_l1 / err_l2 / err_linf of rmhd_result for the HOST field u [ne_owned][ndof] against the exact field at
+ * time t_exact: err[3] = (sum |e| w, sum e^2 w, max |e|) of this rank's elements (the driver reduces them and takes the root of the
+ * second).  0, or -1 with the reason in rmhd_last_error where the case has no exact field -- another problem than 0 / 4, remap mode, a
+ * non-periodic mesh for the translation, or an unstructured mesh file: the driver then reports has_errors = 0. */
+int rmhd_case_lp_errors(const rmhd_case *c, double t_exact, const double *u, double err[3]);
 
 typedef struct {
    double final_mass, max_value, mass0, mass_loss; /* remhos.cpp:1423-1428 */

@@ -22,7 +22,7 @@ SYMBOLS = [
     "rmh_dt_estimate_reset", "rmh_dt_estimate_update", "rmh_dt_estimate_get", "rmh_invalidate_extrema",
     "rmh_exchange_setup", "rmh_comm_unique_id", "rmh_comm_init", "rmh_comm_attach", "rmh_comm_connect_local",
     "rmh_exchange_begin", "rmh_exchange_end", "rmh_exchange_minmax_begin", "rmh_exchange_minmax_end", "rmh_exchange_buffers", "rmh_exchange_peer", "rmh_allreduce", "rmh_comm_count",
-    "rmh_build_tables", "rmh_build_tables_2d", "rmh_product_ratio", "rmh_elem_minmax_masked", "rmh_fct_product",
+    "rmh_build_tables", "rmh_build_tables_2d", "rmh_build_tables_quad", "rmh_set_quad_topology", "rmh_product_ratio", "rmh_elem_minmax_masked", "rmh_fct_product",
     "rmh_check_violation",
 ]
 
@@ -157,6 +157,8 @@ def load_library(path: str | None = None) -> C.CDLL:
     lib.rmh_allreduce.argtypes = [p, C.POINTER(d), i, i]
     lib.rmh_build_tables.argtypes = [i, i, p, p, p]
     lib.rmh_build_tables_2d.argtypes = [i, i, p, p, p]
+    lib.rmh_build_tables_quad.argtypes = [i, p, p, p, p, p]
+    lib.rmh_set_quad_topology.argtypes = [p, p, p, p]
     lib.rmh_product_ratio.argtypes = [p, p, p, p, p, p]
     lib.rmh_elem_minmax_masked.argtypes = [p, p, p, p, p, p]
     lib.rmh_fct_product.argtypes = [p, p, p, p, p, p, p, p, p, d, p]
@@ -175,17 +177,49 @@ def _ptr(x):
     return x.ctypes.data
 
 
+def build_tables_quad(lib, elem_vertices):
+    """rmh_build_tables_quad (include/rmh.h) for elem_vertices [ne][4] (corner k = kx + 2 ky): returns face_nbr [ne][4] int32 and the
+    quad_topology tuple (face_code [ne][4] uint8, corner_ptr [4 ne + 1] int32, corner_elems int32) that Context takes.  `lib`: any of
+    the libraries as load_library / case.bind_driver hand them out (host code, no GPU)."""
+    import numpy as np
+
+    ev = np.ascontiguousarray(elem_vertices, dtype=np.int32)
+    ne = ev.shape[0]
+    assert ev.shape == (ne, 4)
+    nbr = np.zeros((ne, 4), dtype=np.int32)
+    code = np.zeros((ne, 4), dtype=np.uint8)
+    ptr = np.zeros(4 * ne + 1, dtype=np.int32)
+
+    def call(corner_elems):
+        rc = lib.rmh_build_tables_quad(ne, ev.ctypes.data, nbr.ctypes.data, code.ctypes.data, ptr.ctypes.data, corner_elems)
+        if rc != 0:
+            lib.rmhd_last_error.restype = C.c_char_p
+            raise RmhError(f"rmh error {rc}: {lib.rmhd_last_error().decode()}")
+
+    call(None)  # corner_ptr alone: the size of corner_elems
+    els = np.zeros(int(ptr[-1]), dtype=np.int32)
+    if els.size:
+        call(els.ctypes.data)
+    return nbr, (code, ptr, els)
+
+
 class Context:
     """One rmh_ctx: thin, argument-checking wrapper.  Vector arguments are torch CUDA tensors
     (or host numpy arrays when `lib` is the g++ emulation build used by the CPU tests)."""
 
-    def __init__(self, lib, *, order, exec_mode, x0, vel, face_nbr, stencil27, ne_ghost=0,
-                 subcell_vel=None, device=0, mesh_order=2):
+    def __init__(self, lib, *, order, exec_mode, x0, vel, face_nbr, stencil27=None, ne_ghost=0,
+                 subcell_vel=None, device=0, mesh_order=2, quad_topology=None):
+        """quad_topology = (face_code [ne][4] uint8, corner_ptr [4 ne + 1], corner_elems): an unstructured quadrilateral mesh
+        (rmh_build_tables_quad / build_tables_quad below); stencil27 may then be left out."""
         import numpy as np
 
         self.lib = lib
         self._keep = []
         ne = face_nbr.shape[0]
+        if stencil27 is None:
+            assert quad_topology is not None, "a lattice context needs its element stencil"
+            stencil27 = np.full((ne, 9), -1, dtype=np.int32)
+            stencil27[:, 4] = np.arange(ne)
         x0 = np.ascontiguousarray(x0, dtype=np.float64)
         vel = np.ascontiguousarray(vel, dtype=np.float64)
         face_nbr = np.ascontiguousarray(face_nbr, dtype=np.int32)
@@ -209,6 +243,13 @@ class Context:
         h = C.c_void_p()
         self._check(lib.rmh_create(C.byref(L), C.byref(h)))
         self.h = h
+        if quad_topology is not None:
+            code, ptr, els = quad_topology
+            code = np.ascontiguousarray(code, dtype=np.uint8)
+            ptr = np.ascontiguousarray(ptr, dtype=np.int32)
+            els = np.ascontiguousarray(els, dtype=np.int32)
+            assert dim == 2 and code.shape == (ne, 4) and ptr.shape == (4 * ne + 1,) and els.shape == (int(ptr[-1]),)
+            self._check(lib.rmh_set_quad_topology(h, code.ctypes.data, ptr.ctypes.data, els.ctypes.data if els.size else None))
 
     def _check(self, rc):
         if rc != 0:

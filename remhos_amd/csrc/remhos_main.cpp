@@ -4,6 +4,8 @@
 //   remhos_amd -m periodic-cube -p 10 -rs 4 -o 3 -dt -1 -tf 0.5 -ms 20 -ho 3 -lo 5 -fct 2 -pa [-bt 1 -dtc 1]   (-fct 4: element FCT projection, -ho 1 / -lo 1 / -lo 2 / -fct 1: NeumannHOSolver / DiscreteUpwind / its preconditioned form / FluxBasedFCT; granular sequence;
 //   -mono 1: MonoRDSolver, the whole stage as one monolithic residual-distribution update -- -ho / -lo / -fct are then ignored)
 //   remhos_amd -m data/periodic-segment.mesh -p 0 -rs 3 -o 3 -dt 0.001 -tf 1 -ho 3 -lo 4 -fct 2    (dim = 1: -ho 2|3, -lo 3|4|5, -fct 2)
+//   remhos_amd -m tests/golden/meshes/star-q2.mesh -pa -p 14 -rs 1 -o 3 -dt -1 -tf 0.5 -ho 3 -lo 5 -fct 2 -ms 5   (a name that is not built in:
+//   the unstructured quadrilateral mesh of the file -- -ho 2|3, -lo 3|4|5, -fct 2; the granular sequence is selected here)
 #include "../../include/rmh_driver.h"
 
 #include <cstdio>
@@ -28,11 +30,19 @@ int main(int argc, char **argv)
       {
          // accept "data/periodic-cube.mesh" as well as the bare lattice name
          std::string m = next();
+         // (the path itself: a name that is not built in is read from it -- an unstructured quadrilateral mesh, rmh_driver.h)
+         const std::string path = m;
          const size_t s = m.find_last_of('/');
          if (s != std::string::npos) { m = m.substr(s + 1); }
          const size_t d = m.rfind(".mesh");
          if (d != std::string::npos) { m = m.substr(0, d); }
          std::snprintf(c.mesh, sizeof(c.mesh), "%s", m.c_str());
+         c.mesh_file[0] = 0;
+         if (!rmhd_is_builtin_mesh(c.mesh))
+         {
+            if (path.size() >= sizeof(c.mesh_file)) { std::fprintf(stderr, "remhos_amd: the path of the mesh file is too long (%zu bytes at most)\n", sizeof(c.mesh_file) - 1); return 1; }
+            std::snprintf(c.mesh_file, sizeof(c.mesh_file), "%s", path.c_str());
+         }
       }
       else if (a == "-rs") { c.rs = std::atoi(next()); }
       else if (a == "-o") { c.order = std::atoi(next()); }
@@ -99,6 +109,9 @@ int main(int argc, char **argv)
    c.ho_type = ho;
    c.fct_type = fct;
    if (fct == 4 || fct == 1 || c.lo_type == 1 || c.lo_type == 2) { c.fused = 0; } // (the fused limiter and the one-kernel stage have their LO solver and clip + scale built in)
+   // a mesh that is read from its file (none of the case builder's lattice names; unstructured quadrilaterals) runs the granular
+   // solver sequence: the fused limiter and the one-kernel stage are the lattices'
+   if (c.mesh_file[0]) { c.fused = 0; }
    rmhd_result r;
    // box-partitioned runs: all blocks in this process (no -comm-file), or one block per process over RCCL
    //   for r in 0 1; do remhos_amd_run ... -px 2 -rank $r -dev $r -comm-file /tmp/rmh.id & done

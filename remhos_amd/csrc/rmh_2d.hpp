@@ -28,6 +28,9 @@ struct Ho2Args
    const double *x0;     // [ne][2][9] mesh nodes, node a = ax + 3 ay
    const double *vel;    // [ne][2][9] remap: displacement; transport: nodal velocity
    const int *face_nbr;  // [ne][4], face f = 2 c + side; neighbour element or -1
+   const unsigned char *face_code; // [ne][4] or null (lattices: the neighbour sees face f as f ^ 1, same tangential direction);
+                                   // bits 0-1: the neighbour's local face g = 2 c' + side', bit 2: its tangential parameter runs
+                                   // the other way (unstructured quadrilaterals, rmh_set_quad_topology)
    const double *tab;    // TabLayout2<P>
    double *du;           // [ne][D2]
    double *m;            // [ne][D2] lumped mass
@@ -75,11 +78,15 @@ __global__ void __launch_bounds__(64) ho2d_kernel(Ho2Args a)
       if (tid < D2) { sU[tid] = a.u[e * D2 + tid]; }
       if (tid < 4 * D)
       {
-         // the neighbour sees face (c, side) as (c, 1 - side) with the same tangential orientation: its face layer
-         const int f = tid / D, it = tid % D, c = f / 2, side = f % 2;
+         // the neighbour sees face (c, side) as (c, 1 - side) with the same tangential orientation: its face layer -- or, with
+         // a code table, as the face (c', side') of the code, walked backwards when the flip bit is set (own geometry, own
+         // normals and the face quadrature stay: the Bernstein face basis is symmetric under the reversal)
+         const int f = tid / D, it = tid % D;
          const int nb = a.face_nbr[e * 4 + f];
-         const int layer = side == 0 ? P : 0;
-         const int dof = c == 0 ? layer + D * it : it + D * layer;
+         const int code = a.face_code ? a.face_code[e * 4 + f] : (f ^ 1);
+         const int c = (code >> 1) & 1, itn = (code & 4) ? P - it : it;
+         const int layer = (code & 1) ? P : 0;
+         const int dof = c == 0 ? layer + D * itn : itn + D * layer;
          sN[f][it] = nb >= 0 ? a.u[(size_t)nb * D2 + dof] : 0.0; // boundary: u_nbr := 0
       }
    }

@@ -12,6 +12,7 @@
 #include "rmh_neumann.hpp"
 #include "rmh_mono.hpp"
 #include "rmh_product2d.hpp"
+#include "rmh_bounds2d.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -317,6 +318,11 @@ int launch_stage_fused(rmh_ctx *c, const double *u, double dt, const double *x_b
 #define RMH_NOT_1D(c, name)                                                                                               \
    if ((c)->dim == 1) { return fail(RMH_ERR_INVALID, name ": not available for dim = 1 (HO solver -ho 2|3, LO solvers -lo 3|4|5, clip + scale, one-kernel stage)"); }
 
+// entry points that read face_nbr / stencil27 with the lattice rule (the neighbour sees face f as f ^ 1 with the same tangential
+// direction; a 3 x 3 element stencil): not for a context that carries the tables of rmh_set_quad_topology
+#define RMH_NOT_UNSTRUCTURED(c, name)                                                                                     \
+   if ((c)->d_face_code) { return fail(RMH_ERR_INVALID, name ": not available on an unstructured quadrilateral context (rmh_set_quad_topology): the entry reads the neighbour tables with the lattice rule"); }
+
 // dim = 1 (rmh_1d.hpp): nodes [ne][3], face_nbr [ne][2], the stencil (e - 1, e, e + 1) [ne][3]; one lane per element
 constexpr int SEG_NT = 64;
 inline int seg_grid(const rmh_ctx *c) { return (c->ne + SEG_NT - 1) / SEG_NT; }
@@ -414,6 +420,7 @@ int launch_ho_2d(rmh_ctx *c, const double *u, double *du, double *m, double t, i
    a.x0 = c->d_x0;
    a.vel = c->d_vel;
    a.face_nbr = c->d_nbr;
+   a.face_code = c->d_face_code; // (null: a lattice)
    a.tab = c->d_tab;
    a.du = du;
    a.m = m;
@@ -738,7 +745,7 @@ void rmh_destroy(rmh_ctx *c)
    if (!c) { return; }
    (void)hipSetDevice(c->device);
    exchange_free(c);
-   void *bufs[] = {c->d_x0, c->d_vel, c->d_x0h, c->d_velh, c->d_tab, c->d_subvel, c->d_subx0, c->d_subvmid, c->d_fgeo, c->d_face_rows, c->d_m, c->d_scr_ho, c->d_scr_lo, c->d_xe_min, c->d_xe_max, c->d_xe_min2, c->d_xe_max2, c->d_nbr, c->d_st27, c->d_cg, c->d_dt_est, c->d_viol, c->d_nm_rhs, c->d_nm_wdet, c->d_nm_part, c->d_nm_norms, c->d_nm_ctl, c->d_mono_rec};
+   void *bufs[] = {c->d_x0, c->d_vel, c->d_x0h, c->d_velh, c->d_tab, c->d_subvel, c->d_subx0, c->d_subvmid, c->d_fgeo, c->d_face_rows, c->d_m, c->d_scr_ho, c->d_scr_lo, c->d_xe_min, c->d_xe_max, c->d_xe_min2, c->d_xe_max2, c->d_nbr, c->d_st27, c->d_cg, c->d_dt_est, c->d_viol, c->d_nm_rhs, c->d_nm_wdet, c->d_nm_part, c->d_nm_norms, c->d_nm_ctl, c->d_mono_rec, c->d_face_code, c->d_corner_ptr, c->d_corner_elems};
    for (void *b : bufs) { (void)hipFree(b); }
    for (int b = 0; b < 4; b++)
    {
@@ -954,6 +961,15 @@ int rmh_bounds(rmh_ctx *c, const double *xe_min, const double *xe_max, double *u
       RMH_HIP(hipGetLastError());
       return RMH_OK;
    }
+   if (c->d_face_code)
+   {
+      // unstructured quadrilaterals: face neighbours and the CSR rows of the element corners (rmh_bounds2d.hpp)
+      RMH_DISPATCH(c, hipLaunchKernelGGL((bounds_quad_kernel<P>), dim3(P2Cfg<P>::grid(c->ne)), dim3(P2Cfg<P>::NT), 0, c->stream,
+                                         c->bounds_type, (const int *)c->d_nbr, (const int *)c->d_corner_ptr,
+                                         (const int *)c->d_corner_elems, xe_min, xe_max, u_min, u_max, c->ne));
+      RMH_HIP(hipGetLastError());
+      return RMH_OK;
+   }
    const int wide = (((uintptr_t)u_min | (uintptr_t)u_max) & 15) == 0; // 16-byte stores
    RMH_DISPATCH_PD(c, hipLaunchKernelGGL((bounds_kernel<P, DIM>), dim3(SCfg<P, DIM>::grid(c->ne, SCfg<P, DIM>::UB)), dim3(SCfg<P, DIM>::NT), 0,
                                          c->stream, c->bounds_type, (const int *)c->d_st27, c->ne, xe_min, xe_max, c->gh_min, c->gh_max,
@@ -1004,6 +1020,7 @@ int rmh_lo_upwind(rmh_ctx *c, const double *u, double *du_lo)
 {
    if (!c || !u || !du_lo) { return fail(RMH_ERR_INVALID, "null argument"); }
    RMH_NOT_1D(c, "rmh_lo_upwind (-lo 1)");
+   RMH_NOT_UNSTRUCTURED(c, "rmh_lo_upwind (-lo 1)");
    if (int rc = ghost_u_ready(c)) { return rc; }
    RMH_ENTER(c);
    extrema_dropped(c);
@@ -1020,6 +1037,7 @@ int rmh_lo_upwind_prec(rmh_ctx *c, const double *u, double *du_lo)
 {
    if (!c || !u || !du_lo) { return fail(RMH_ERR_INVALID, "null argument"); }
    RMH_NOT_1D(c, "rmh_lo_upwind_prec (-lo 2)");
+   RMH_NOT_UNSTRUCTURED(c, "rmh_lo_upwind_prec (-lo 2)");
    if (c->dim == 3 && c->p >= 4)
    {
       return fail(RMH_ERR_INVALID, "rmh_lo_upwind_prec (-lo 2): order " + std::to_string(c->p) +
@@ -1050,6 +1068,7 @@ int rmh_mono_rd(rmh_ctx *c, const double *u, const double *xi_min, const double 
 {
    if (!c || !u || !xi_min || !xi_max || !scale || !du) { return fail(RMH_ERR_INVALID, "null argument"); }
    RMH_NOT_1D(c, "rmh_mono_rd (-mono 1)");
+   RMH_NOT_UNSTRUCTURED(c, "rmh_mono_rd (-mono 1)");
    if (c->ng > 0)
    {
       return fail(RMH_ERR_INVALID, "rmh_mono_rd (-mono 1): contexts with ghost elements are not supported (the solver runs on one block)");
@@ -1107,6 +1126,7 @@ int rmh_ho_neumann(rmh_ctx *c, const double *u, double *du)
 {
    if (!c || !u || !du) { return fail(RMH_ERR_INVALID, "null argument"); }
    RMH_NOT_1D(c, "rmh_ho_neumann (-ho 1)");
+   RMH_NOT_UNSTRUCTURED(c, "rmh_ho_neumann (-ho 1)");
    if (c->ng > 0)
    {
       return fail(RMH_ERR_INVALID, "rmh_ho_neumann (-ho 1): contexts with ghost elements are not supported (the global residual norm would need a reduction over the ranks: the solver runs on one rank)");
@@ -1163,6 +1183,7 @@ int rmh_fct_fluxbased(rmh_ctx *c, const double *u, const double *m, const double
 {
    if (int rc = check_limiter_args(c, u, m, du_ho, du_lo, u_min, u_max, du)) { return rc; }
    RMH_NOT_1D(c, "rmh_fct_fluxbased (-fct 1)");
+   RMH_NOT_UNSTRUCTURED(c, "rmh_fct_fluxbased (-fct 1)");
    if (!(dt > 0.0)) { return fail(RMH_ERR_INVALID, "dt must be positive"); }
    if (c->ng > 0)
    {
@@ -1251,6 +1272,7 @@ static int limit_fused_impl(rmh_ctx *c, const double *u, const double *du_ho, co
                             const double *x_base, double a, double b, double dt_rk, double *y_out)
 {
    if (!c || !u || !du_ho || (!du && !y_out)) { return fail(RMH_ERR_INVALID, "null argument"); }
+   RMH_NOT_UNSTRUCTURED(c, "rmh_limit_fused / rmh_limit_fused_lo");
    if (!c->ho_done) { return fail(RMH_ERR_STATE, "rmh_limit_fused must follow rmh_ho_apply on the same u"); }
    RMH_ENTER(c);
    extrema_dropped(c);
@@ -1327,6 +1349,7 @@ int rmh_stage_fused_chain(rmh_ctx *c, const double *u, double dt, const double *
 {
    if (out_token) { *out_token = 0; }
    if (!c || !u || !y_out) { return fail(RMH_ERR_INVALID, "null argument"); }
+   RMH_NOT_UNSTRUCTURED(c, "rmh_stage_fused");
    RMH_ENTER(c);
    if (!(dt > 0.0)) { return fail(RMH_ERR_INVALID, "dt must be positive"); }
    if (y_out == u || du == u) { return fail(RMH_ERR_INVALID, "rmh_stage_fused: the output must not alias u"); }
@@ -1529,6 +1552,39 @@ int rmh_set_bounds_type(rmh_ctx *c, int bounds_type)
 {
    if (!c || (bounds_type != 0 && bounds_type != 1)) { return fail(RMH_ERR_INVALID, "Wrong option for bounds computation."); }
    c->bounds_type = bounds_type;
+   return RMH_OK;
+}
+
+int rmh_set_quad_topology(rmh_ctx *c, const unsigned char *face_code, const int *corner_ptr, const int *corner_elems)
+{
+   if (!c || !face_code || !corner_ptr) { return fail(RMH_ERR_INVALID, "rmh_set_quad_topology: null argument"); }
+   if (c->dim != 2 || c->ng != 0) { return fail(RMH_ERR_INVALID, "rmh_set_quad_topology: a dim = 2 context without ghost elements"); }
+   if (c->d_face_code) { return fail(RMH_ERR_STATE, "rmh_set_quad_topology: the context already has its tables"); }
+   RMH_ENTER(c);
+   // the kernels index u and the element extrema with these tables: reject anything out of range
+   const size_t ne = c->ne;
+   for (size_t k = 0; k < 4 * ne; k++)
+   {
+      if (face_code[k] > 7) { return fail(RMH_ERR_INVALID, "rmh_set_quad_topology: face_code entry out of range (bits 0-1 face, bit 2 flip)"); }
+      if (corner_ptr[k + 1] < corner_ptr[k]) { return fail(RMH_ERR_INVALID, "rmh_set_quad_topology: corner_ptr must not decrease"); }
+   }
+   if (corner_ptr[0] != 0) { return fail(RMH_ERR_INVALID, "rmh_set_quad_topology: corner_ptr must start at 0"); }
+   const size_t nce = (size_t)corner_ptr[4 * ne];
+   if (nce > 0 && !corner_elems) { return fail(RMH_ERR_INVALID, "rmh_set_quad_topology: null corner_elems"); }
+   for (size_t j = 0; j < nce; j++)
+   {
+      if (corner_elems[j] < 0 || (size_t)corner_elems[j] >= ne) { return fail(RMH_ERR_INVALID, "rmh_set_quad_topology: corner_elems entry out of range"); }
+   }
+   int rc = 0;
+   int *d_ptr = nullptr, *d_el = nullptr;
+   if ((rc = upload(&d_ptr, corner_ptr, 4 * ne + 1))) { return rc; }
+   const int none = 0; // (a mesh of one element: an empty list still gets a valid pointer)
+   if ((rc = upload(&d_el, nce ? corner_elems : &none, nce ? nce : 1))) { (void)hipFree(d_ptr); return rc; }
+   if ((rc = upload(&c->d_face_code, face_code, 4 * ne))) { (void)hipFree(d_ptr); (void)hipFree(d_el); (void)hipFree(c->d_face_code); c->d_face_code = nullptr; return rc; }
+   c->d_corner_ptr = d_ptr;
+   c->d_corner_elems = d_el;
+   c->ho_done = false;
+   extrema_dropped(c);
    return RMH_OK;
 }
 

@@ -39,6 +39,7 @@ CaseConfig to_config(const rmhd_config &c)
    for (int d = 0; d < 3; d++) { k.rs_extra[d] = c.rs_extra[d]; }
    k.self_wrap = c.self_wrap;
    k.tile_rows = c.tile_rows > 0 ? c.tile_rows : 0;
+   k.mesh_file = std::string(c.mesh_file, strnlen(c.mesh_file, sizeof(c.mesh_file)));
    return k;
 }
 } // namespace remhos
@@ -86,6 +87,8 @@ int rmhd_case_get_info(const rmhd_case *c, rmhd_case_info *info)
       info->bb_max[k] = d.bb_max[k];
    }
    info->dt = d.dt;
+   info->unstructured = d.unstructured ? 1 : 0;
+   info->n_corner_elems = (int)d.corner_elems.size();
    return 0;
 }
 
@@ -105,6 +108,10 @@ const double *rmhd_case_mono_scale(rmhd_case *c)
 }
 const int *rmhd_case_face_nbr(const rmhd_case *c) { return c->d.face_nbr.data(); }
 const int *rmhd_case_stencil27(const rmhd_case *c) { return c->d.stencil27.data(); }
+const int *rmhd_case_elem_vertices(const rmhd_case *c) { return c->d.elem_vertices.empty() ? nullptr : c->d.elem_vertices.data(); }
+const unsigned char *rmhd_case_face_code(const rmhd_case *c) { return c->d.face_code.empty() ? nullptr : c->d.face_code.data(); }
+const int *rmhd_case_corner_ptr(const rmhd_case *c) { return c->d.corner_ptr.empty() ? nullptr : c->d.corner_ptr.data(); }
+const int *rmhd_case_corner_elems(const rmhd_case *c) { return c->d.corner_elems.empty() ? nullptr : c->d.corner_elems.data(); }
 const long long *rmhd_case_owned_gid(const rmhd_case *c) { return c->d.owned_gid.data(); }
 const long long *rmhd_case_ghost_gid(const rmhd_case *c) { return c->d.ghost_gid.data(); }
 
@@ -134,6 +141,17 @@ int rmhd_case_save(const rmhd_case *c, double t, const double *u, const char *me
    return 0;
 }
 
+
+int rmhd_is_builtin_mesh(const char *name) { return name && remhos::is_builtin_mesh(name) ? 1 : 0; }
+
+// the error sums the driver's report is made of (remhos::lp_error_sums), or why the case has none
+int rmhd_case_lp_errors(const rmhd_case *c, double t_exact, const double *u, double err[3])
+{
+   if (!c || !u || !err) { remhos::g_driver_error = "rmhd_case_lp_errors: null argument"; return -1; }
+   const std::string why = remhos::lp_error_sums(c->d, c->problem, t_exact, u, err);
+   if (!why.empty()) { remhos::g_driver_error = why; return -1; }
+   return 0;
+}
 
 // include/rmh.h: neighbour tables from the vertex ids of the elements (any element numbering); DIM = 3: 8 corners, 6 faces,
 // 27-entry stencil; DIM = 2: 4 corners, 4 faces, 9-entry stencil
@@ -196,6 +214,21 @@ int rmh_build_tables(int ne_owned, int ne_total, const int *ev, int *face_nbr, i
 int rmh_build_tables_2d(int ne_owned, int ne_total, const int *ev, int *face_nbr, int *stencil9)
 {
    return build_tables_dim<2>(ne_owned, ne_total, ev, face_nbr, stencil9);
+}
+
+// include/rmh.h: the tables of an unstructured quadrilateral mesh (remhos::quad_topology, rmh_host.cpp)
+int rmh_build_tables_quad(int ne, const int *ev, int *face_nbr, unsigned char *face_code, int *corner_ptr, int *corner_elems)
+{
+   if (ne <= 0 || !ev || !face_nbr || !face_code || !corner_ptr) { remhos::g_driver_error = "rmh_build_tables_quad: bad argument"; return RMH_ERR_INVALID; }
+   std::vector<int> nbr, ptr, els;
+   std::vector<unsigned char> code;
+   const std::string err = remhos::quad_topology(ne, ev, nbr, code, ptr, els);
+   if (!err.empty()) { remhos::g_driver_error = "rmh_build_tables_quad: " + err; return RMH_ERR_INVALID; }
+   std::copy(nbr.begin(), nbr.end(), face_nbr);
+   std::copy(code.begin(), code.end(), face_code);
+   std::copy(ptr.begin(), ptr.end(), corner_ptr);
+   if (corner_elems) { std::copy(els.begin(), els.end(), corner_elems); }
+   return RMH_OK;
 }
 
 } // extern "C"

@@ -57,6 +57,10 @@ struct rmh_ctx
    const double *stage_u = nullptr; // input vector and step of the open stage (its ranges must agree)
    double stage_dt = 0.0;
    int *d_nbr = nullptr, *d_st27 = nullptr, *d_cg = nullptr;
+   // dim = 2, unstructured quadrilaterals (rmh_set_quad_topology; null on lattice contexts): the neighbour's local face and the
+   // flip bit of every face [ne][4], and the CSR rows of the other elements at every element corner (rmh_bounds2d.hpp)
+   unsigned char *d_face_code = nullptr;
+   int *d_corner_ptr = nullptr, *d_corner_elems = nullptr;
    const double *u_ghost = nullptr, *gh_min = nullptr, *gh_max = nullptr;
    int layer_stride = 0;      // dim = 3: the usual distance e' - e of an element to its +z face neighbour (the elements of one lattice layer);
                               // 0: no such structure -- the stage kernel then keeps contiguous eighths per XCD (xcd_chunk_for, rmh_api.hip)

@@ -346,6 +346,38 @@ static int check_dim1(const rmhd_config *cfg, bool partitioned)
    return -1;
 }
 
+// An unstructured quadrilateral mesh from a file (rmhd_config.mesh_file; data/star-q2.mesh, data/periodic-hexagon.mesh): the name is
+// none of the built-in lattices and the file can be opened.  (Neither: the case builder answers "unknown lattice mesh".)  Such a run
+// takes -ho 2|3 [-pa], -lo 3|4|5, -fct 2, -bt, -dtc, -vb, -s 3 on one block through the granular solver sequence; every other option
+// is refused here, before a device context exists (0 on success, else the message is in g_driver_error)
+static bool is_file_mesh(const rmhd_config *cfg)
+{
+   if (is_builtin_mesh(std::string(cfg->mesh, strnlen(cfg->mesh, sizeof(cfg->mesh)))) || !cfg->mesh_file[0]) { return false; }
+   if (strnlen(cfg->mesh_file, sizeof(cfg->mesh_file)) == sizeof(cfg->mesh_file)) { return false; }
+   FILE *f = std::fopen(cfg->mesh_file, "r");
+   if (f) { std::fclose(f); }
+   return f != nullptr;
+}
+static int check_unstructured(const rmhd_config *cfg, bool partitioned)
+{
+   const char *why = nullptr;
+   const int ode = cfg->ode_solver, lo = cfg->lo_type, fct = cfg->fct_type;
+   if (partitioned || cfg->px > 1 || cfg->py > 1 || cfg->pz > 1 || cfg->rank != 0) { why = "partitions (px, py, pz, rank): box-partitioned runs are"; }
+   else if (cfg->mono_type) { why = "mono_type (-mono): the monolithic RD solver is"; }
+   else if (cfg->fused) { why = "fused = 1: the fused limiter and the one-kernel stage (they read the neighbour tables with the lattice rule) are"; }
+   else if (cfg->ho_type == 1) { why = "ho_type 1 (-ho 1): the Neumann HO solver is"; }
+   else if (lo == 1 || lo == 2) { why = "lo_type 1|2 (-lo 1|2): the DiscreteUpwind LO solvers are"; }
+   else if (fct == 1) { why = "fct_type 1 (-fct 1): the flux-based FCT solver is"; }
+   else if (fct == 4) { why = "fct_type 4 (-fct 4): the element FCT projection is"; }
+   else if (cfg->ps) { why = "ps (-ps): product remap is"; }
+   else if (ode != 0 && ode != 3) { why = "ode_solver (-s 11|12|13): the IDP solvers are"; }
+   else if (cfg->self_wrap) { why = "self_wrap: the self-wrapped halo is"; }
+   else if (cfg->save) { why = "save (-save): the MFEM mesh / field writer is"; }
+   if (!why) { return 0; }
+   g_driver_error = std::string(why) + " not available on an unstructured mesh file (-ho 2|3 [-pa], -lo 3|4|5, -fct 2, -bt 0|1, -dtc 0|1, -vb, -s 3, one block, fused = 0)";
+   return -1;
+}
+
 // remhos.cpp:1557-1594
 static void report_violation(const rmh_violation &v, const std::string &info)
 {
@@ -703,6 +735,7 @@ extern "C" int rmhd_run_rank(const rmhd_config *cfg, const char *comm_id_file, i
          cfg = &seg_cfg;
       }
    }
+   if (is_file_mesh(cfg) && check_unstructured(cfg, false) != 0) { return -1; }
    if (check_mono_type(cfg, false) != 0) { return -1; }
    rmhd_config mono_cfg;
    if (cfg->mono_type)
@@ -765,6 +798,12 @@ extern "C" int rmhd_run_rank(const rmhd_config *cfg, const char *comm_id_file, i
    L.device = device;
    rmh_ctx *ctx = nullptr;
    if (rmh_create(&L, &ctx) != 0) { g_driver_error = rmh_last_error(); return -1; }
+   if (cd.unstructured && rmh_set_quad_topology(ctx, cd.face_code.data(), cd.corner_ptr.data(), cd.corner_elems.data()) != 0)
+   {
+      g_driver_error = rmh_last_error();
+      rmh_destroy(ctx);
+      return -1;
+   }
    rmh_enable_timers(ctx, 1);
    bool reduce_over_ranks = false;
    if (cd.ne_ghost > 0)
@@ -1269,6 +1308,7 @@ extern "C" int rmhd_run_partitioned(const rmhd_config *cfg, const char *comm_id_
    const int nranks = cc0.px * cc0.py * cc0.pz;
    const bool rccl = comm_id_file && comm_id_file[0];
    if (is_segment_mesh(cfg) && check_dim1(cfg, true) != 0) { return -1; }
+   if (is_file_mesh(cfg) && check_unstructured(cfg, true) != 0) { return -1; }
    if (check_mono_type(cfg, true) != 0) { return -1; }
    if (check_fct_type(cfg, true) != 0) { return -1; }
    if (!cfg->fused) { g_driver_error = "rmhd_run_partitioned runs the one-kernel stage (fused = 1)"; return -1; }

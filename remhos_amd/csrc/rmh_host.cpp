@@ -522,12 +522,519 @@ static std::string build_case_1d(const CaseConfig &cfg, CaseData &out)
    return "";
 }
 
+// ---- dim = 2 from a mesh file: unstructured quadrilaterals -----------------------------------------------------------
+bool is_builtin_mesh(const std::string &name)
+{
+   MeshDef md;
+   return name == "periodic-segment" || name == "inline-quad" || name == "periodic-square" || lookup_mesh(name, md);
+}
+
+// Topology of a conforming quadrilateral mesh from the vertex ids of its elements (include/rmh.h, rmh_build_tables_quad).  A face
+// f = 2 c + side runs from corner FC[f][0] to corner FC[f][1] (corner k = kx + 2 ky) along its increasing tangential parameter.
+std::string quad_topology(int ne, const int *ev, std::vector<int> &face_nbr, std::vector<unsigned char> &face_code,
+                          std::vector<int> &corner_ptr, std::vector<int> &corner_elems)
+{
+   static const int FC[4][2] = {{0, 2}, {1, 3}, {0, 1}, {2, 3}};
+   if (ne <= 0 || !ev) { return "no elements"; }
+   face_nbr.assign((size_t)ne * 4, -1);
+   face_code.assign((size_t)ne * 4, 0);
+   std::map<std::pair<int, int>, std::vector<int>> edges; // sorted vertex pair -> faces 4 e + f
+   std::map<int, std::vector<int>> v2e;                   // vertex -> elements, ascending
+   for (int e = 0; e < ne; e++)
+   {
+      const int *v = ev + (size_t)e * 4;
+      for (int k = 0; k < 4; k++)
+      {
+         for (int j = k + 1; j < 4; j++)
+         {
+            if (v[k] == v[j]) { return "element " + std::to_string(e) + " names vertex " + std::to_string(v[k]) + " twice (degenerate, or a periodic mesh that is too coarse)"; }
+         }
+         v2e[v[k]].push_back(e);
+      }
+      for (int f = 0; f < 4; f++)
+      {
+         const int a = v[FC[f][0]], b = v[FC[f][1]];
+         edges[{std::min(a, b), std::max(a, b)}].push_back(4 * e + f);
+      }
+   }
+   for (const auto &kv : edges)
+   {
+      const std::vector<int> &l = kv.second;
+      if (l.size() == 1) { continue; } // domain boundary
+      const int e = l[0] / 4, f = l[0] % 4, g = l[1] / 4, h = l[1] % 4;
+      if (e == g) { return "element " + std::to_string(e) + " is its own neighbour (faces " + std::to_string(f) + " and " + std::to_string(h) + ")"; }
+      if (l.size() > 2)
+      {
+         return "the vertex pair (" + std::to_string(kv.first.first) + ", " + std::to_string(kv.first.second) + ") bounds " + std::to_string(l.size()) +
+                " element faces: not a conforming mesh, or a periodic mesh that is too coarse";
+      }
+      const int flip = ev[(size_t)e * 4 + FC[f][0]] != ev[(size_t)g * 4 + FC[h][0]] ? 4 : 0;
+      face_nbr[l[0]] = g;
+      face_code[l[0]] = (unsigned char)(h | flip);
+      face_nbr[l[1]] = e;
+      face_code[l[1]] = (unsigned char)(f | flip);
+   }
+   corner_ptr.assign((size_t)ne * 4 + 1, 0);
+   corner_elems.clear();
+   for (int e = 0; e < ne; e++)
+   {
+      for (int k = 0; k < 4; k++)
+      {
+         for (int g : v2e[ev[(size_t)e * 4 + k]]) { if (g != e) { corner_elems.push_back(g); } }
+         corner_ptr[(size_t)e * 4 + k + 1] = (int)corner_elems.size();
+      }
+   }
+   return "";
+}
+
+namespace
+{
+struct QuadMesh
+{
+   int nv = 0;
+   std::vector<int> ev;   // [ne][4] vertex ids, corner k = kx + 2 ky
+   std::vector<double> X; // [ne][2][9] Q2 nodes, node a = ax + 3 ay
+   int ne() const { return (int)(ev.size() / 4); }
+};
+
+// The subset of "MFEM mesh v1.0" that data/star-q2.mesh and data/periodic-hexagon.mesh use: dimension 2, quadrilaterals, and the
+// coordinates as plain vertices, as an H1 "Quadratic" nodal grid function (vertices, then edges in the order of their first
+// appearance over the elements' local edges (0,1), (1,2), (2,3), (3,0), then element interiors), or as an L2_T1_2D_P1 one (4
+// nodes per element, lexicographic: a periodic mesh, glued through its vertex ids).  Returns false when the file cannot be opened;
+// otherwise err is "" or names what was found instead.
+bool read_quad_mesh(const std::string &path, QuadMesh &m, std::string &err)
+{
+   FILE *fp = std::fopen(path.c_str(), "r");
+   if (!fp) { return false; }
+   std::vector<std::string> L; // lines without comments, trimmed, non-empty
+   {
+      std::string cur;
+      auto flush = [&]()
+      {
+         const size_t a = cur.find_first_not_of(" \t\r"), b = cur.find_last_not_of(" \t\r");
+         if (a != std::string::npos && cur[a] != '#') { L.push_back(cur.substr(a, b - a + 1)); }
+         cur.clear();
+      };
+      for (int ch = std::fgetc(fp); ch != EOF; ch = std::fgetc(fp))
+      {
+         if (ch == '\n') { flush(); }
+         else { cur.push_back((char)ch); }
+      }
+      flush();
+      std::fclose(fp);
+   }
+   err = "";
+   const std::string who = "mesh file '" + path + "': ";
+   size_t i = 0;
+   auto line = [&]() -> std::string { return i < L.size() ? L[i++] : std::string("<end of file>"); };
+   auto numbers = [](const std::string &s, std::vector<double> &v)
+   {
+      const char *p = s.c_str();
+      char *end = nullptr;
+      for (double x = std::strtod(p, &end); end != p; x = std::strtod(p, &end)) { v.push_back(x); p = end; }
+      while (*p == ' ' || *p == '\t') { p++; }
+      return *p == 0;
+   };
+   auto count_after = [&](const char *key, int &n)
+   {
+      const std::string k = line();
+      if (k != key) { err = who + "expected '" + key + "', found '" + k + "'"; return false; }
+      std::vector<double> v;
+      const std::string s = line();
+      if (!numbers(s, v) || v.size() != 1 || v[0] < 0 || v[0] != std::floor(v[0]) || v[0] > 1e8) { err = who + "expected a count after '" + key + "', found '" + s + "'"; return false; }
+      n = (int)v[0];
+      return true;
+   };
+   {
+      const std::string h = line();
+      if (h != "MFEM mesh v1.0") { err = who + "not an \"MFEM mesh v1.0\" file (first line '" + h + "'; NURBS and non-conforming meshes are not read)"; return true; }
+   }
+   int dim = 0, ne = 0, nb = 0;
+   if (!count_after("dimension", dim)) { return true; }
+   if (dim != 2) { err = who + "dimension " + std::to_string(dim) + " (mesh files are read for dimension 2 only)"; return true; }
+   if (!count_after("elements", ne)) { return true; }
+   if (ne < 1) { err = who + "no elements"; return true; }
+   std::vector<int> mv((size_t)ne * 4); // MFEM's vertex order (counter-clockwise)
+   for (int e = 0; e < ne; e++)
+   {
+      std::vector<double> v;
+      const std::string s = line();
+      if (!numbers(s, v) || v.size() < 2) { err = who + "bad element line '" + s + "'"; return true; }
+      if ((int)v[1] != 3)
+      {
+         err = who + "element " + std::to_string(e) + " has geometry type " + std::to_string((int)v[1]) + (v[1] == 2 ? " (triangle)" : "") + ": only quadrilaterals (type 3) are read";
+         return true;
+      }
+      if (v.size() != 6) { err = who + "bad element line '" + s + "'"; return true; }
+      for (int k = 0; k < 4; k++) { mv[(size_t)e * 4 + k] = (int)v[2 + k]; }
+   }
+   if (!count_after("boundary", nb)) { return true; }
+   i += (size_t)nb; // (the boundary is where an edge has one element)
+   if (!count_after("vertices", m.nv)) { return true; }
+   const int nv = m.nv;
+   for (int v : mv) { if (v < 0 || v >= nv) { err = who + "vertex id " + std::to_string(v) + " out of range"; return true; } }
+   // corners P[e][j][c], j = jx + 2 jy, or all 9 nodes for a quadratic space
+   m.ev.resize((size_t)ne * 4);
+   for (int e = 0; e < ne; e++)
+   {
+      const int *v = &mv[(size_t)e * 4];
+      const int lex[4] = {v[0], v[1], v[3], v[2]};
+      std::copy(lex, lex + 4, &m.ev[(size_t)e * 4]);
+   }
+   m.X.assign((size_t)ne * 18, 0.0);
+   auto from_corners = [&](int e, const double P[4][2])
+   {
+      for (int ay = 0; ay < 3; ay++)
+      {
+         for (int ax = 0; ax < 3; ax++)
+         {
+            const double x = 0.5 * ax, y = 0.5 * ay;
+            const double w[4] = {(1 - x) * (1 - y), x * (1 - y), (1 - x) * y, x * y};
+            for (int c = 0; c < 2; c++)
+            {
+               double s = 0.0;
+               for (int j = 0; j < 4; j++) { s += w[j] * P[j][c]; }
+               m.X[((size_t)e * 2 + c) * 9 + ax + 3 * ay] = s;
+            }
+         }
+      }
+   };
+   std::vector<double> vals;
+   if (i < L.size() && L[i] == "nodes")
+   {
+      i++;
+      const std::string fes = line(), fec = line(), vd = line(), ord = line();
+      if (fes != "FiniteElementSpace" || fec.rfind("FiniteElementCollection:", 0) != 0 || vd.rfind("VDim:", 0) != 0 || ord.rfind("Ordering:", 0) != 0)
+      {
+         err = who + "expected the header of a nodal grid function after 'nodes', found '" + fes + "' / '" + fec + "' / '" + vd + "' / '" + ord + "'";
+         return true;
+      }
+      std::string name = fec.substr(24);
+      name.erase(0, name.find_first_not_of(" \t"));
+      const int vdim = std::atoi(vd.c_str() + 5), ordering = std::atoi(ord.c_str() + 9);
+      if (vdim != 2 || (ordering != 0 && ordering != 1)) { err = who + "nodes with '" + vd + "', '" + ord + "' (VDim 2, Ordering 0 or 1)"; return true; }
+      const bool h1q2 = name == "Quadratic" || name == "H1_2D_P2", l2p1 = name == "L2_T1_2D_P1";
+      if (!h1q2 && !l2p1)
+      {
+         err = who + "nodes in the space '" + name + "': only H1 'Quadratic' (H1_2D_P2) and L2_T1_2D_P1 nodes are read";
+         return true;
+      }
+      while (i < L.size()) { const std::string s = line(); if (!numbers(s, vals)) { err = who + "bad number in '" + s + "'"; return true; } }
+      std::map<std::pair<int, int>, int> edge_id;
+      std::vector<std::pair<int, int>> edge_list;
+      if (h1q2)
+      {
+         for (int e = 0; e < ne; e++)
+         {
+            for (int k = 0; k < 4; k++)
+            {
+               const int a = mv[(size_t)e * 4 + k], b = mv[(size_t)e * 4 + (k + 1) % 4];
+               const std::pair<int, int> key(std::min(a, b), std::max(a, b));
+               if (edge_id.emplace(key, (int)edge_list.size()).second) { edge_list.push_back(key); }
+            }
+         }
+      }
+      const size_t ned = edge_list.size(), n = h1q2 ? (size_t)nv + ned + ne : (size_t)4 * ne;
+      if (vals.size() != 2 * n)
+      {
+         err = who + "'" + name + "' nodes: " + std::to_string(vals.size()) + " values, expected 2 x " + std::to_string(n);
+         return true;
+      }
+      auto X = [&](size_t node, int c) { return ordering == 0 ? vals[c * n + node] : vals[2 * node + c]; };
+      if (l2p1)
+      {
+         for (int e = 0; e < ne; e++)
+         {
+            double P[4][2];
+            for (int j = 0; j < 4; j++) { for (int c = 0; c < 2; c++) { P[j][c] = X((size_t)4 * e + j, c); } }
+            from_corners(e, P);
+         }
+      }
+      else
+      {
+         // validity of the assumed dof numbering: the node of every edge is the edge node nearest to its edge's midpoint
+         for (size_t k = 0; k < ned; k++)
+         {
+            const double mx = 0.5 * (X(edge_list[k].first, 0) + X(edge_list[k].second, 0));
+            const double my = 0.5 * (X(edge_list[k].first, 1) + X(edge_list[k].second, 1));
+            size_t best = 0;
+            double dbest = INFINITY;
+            for (size_t j = 0; j < ned; j++)
+            {
+               const double d = std::hypot(X(nv + j, 0) - mx, X(nv + j, 1) - my);
+               if (d < dbest) { dbest = d; best = j; }
+            }
+            if (best != k)
+            {
+               err = who + "the quadratic nodes do not follow the vertex / edge / interior numbering (edge " + std::to_string(k) + " finds the node of edge " + std::to_string(best) + " at its midpoint)";
+               return true;
+            }
+         }
+         for (int e = 0; e < ne; e++)
+         {
+            const int *v = &mv[(size_t)e * 4];
+            auto eid = [&](int a, int b) { return (size_t)nv + edge_id.at({std::min(a, b), std::max(a, b)}); };
+            // MFEM's local order v0 e0 v1 / e3 c e1 / v3 e2 v2, row by row
+            const size_t ids[9] = {(size_t)v[0], eid(v[0], v[1]), (size_t)v[1], eid(v[3], v[0]), (size_t)nv + ned + e, eid(v[1], v[2]), (size_t)v[3], eid(v[2], v[3]), (size_t)v[2]};
+            for (int a = 0; a < 9; a++) { for (int c = 0; c < 2; c++) { m.X[((size_t)e * 2 + c) * 9 + a] = X(ids[a], c); } }
+         }
+      }
+   }
+   else
+   {
+      int vdim = 0;
+      {
+         std::vector<double> v;
+         const std::string s = line();
+         if (!numbers(s, v) || v.size() != 1) { err = who + "expected 'nodes' or the vertex dimension after the vertex count, found '" + s + "'"; return true; }
+         vdim = (int)v[0];
+      }
+      if (vdim != 2) { err = who + "vertices of dimension " + std::to_string(vdim) + " (2 expected)"; return true; }
+      for (int k = 0; k < nv; k++) { const std::string s = line(); if (!numbers(s, vals)) { err = who + "bad vertex line '" + s + "'"; return true; } }
+      if (vals.size() != (size_t)2 * nv) { err = who + "expected " + std::to_string(nv) + " vertex lines of 2 coordinates"; return true; }
+      for (int e = 0; e < ne; e++)
+      {
+         double P[4][2];
+         for (int j = 0; j < 4; j++) { for (int c = 0; c < 2; c++) { P[j][c] = vals[(size_t)2 * m.ev[(size_t)e * 4 + j] + c]; } }
+         from_corners(e, P);
+      }
+   }
+   return true;
+}
+
+// -rs: every element into 2 x 2 children (lexicographic in the parent's axes); a child's nodes are the parent's Q2 map at the child's
+// node points; vertex ids stay topological -- coarse vertex, midpoint of a coarse edge (keyed by its vertex pair), or interior --
+// because a periodic mesh cannot be glued by coordinates
+void refine_quad_mesh(QuadMesh &m)
+{
+   const int ne = m.ne();
+   std::map<std::pair<int, int>, int> mid;
+   int nv = m.nv;
+   auto midv = [&](int a, int b)
+   {
+      const auto r = mid.emplace(std::make_pair(std::min(a, b), std::max(a, b)), nv);
+      if (r.second) { nv++; }
+      return r.first->second;
+   };
+   std::vector<int> ev((size_t)ne * 16);
+   std::vector<double> X((size_t)ne * 72);
+   for (int e = 0; e < ne; e++)
+   {
+      const int *c = &m.ev[(size_t)e * 4];
+      const double *Xp = &m.X[(size_t)e * 18];
+      int g[3][3];
+      g[0][0] = c[0]; g[0][2] = c[1]; g[2][0] = c[2]; g[2][2] = c[3];
+      g[0][1] = midv(c[0], c[1]); g[2][1] = midv(c[2], c[3]); g[1][0] = midv(c[0], c[2]); g[1][2] = midv(c[1], c[3]);
+      g[1][1] = nv++;
+      for (int cy = 0; cy < 2; cy++)
+      {
+         for (int cx = 0; cx < 2; cx++)
+         {
+            const size_t ch = (size_t)e * 4 + cx + 2 * cy;
+            for (int k = 0; k < 4; k++) { ev[ch * 4 + k] = g[cy + (k >> 1)][cx + (k & 1)]; }
+            for (int ay = 0; ay < 3; ay++)
+            {
+               for (int ax = 0; ax < 3; ax++)
+               {
+                  double Lx[3], Ly[3];
+                  lag2(cx * 0.5 + ax * 0.25, Lx);
+                  lag2(cy * 0.5 + ay * 0.25, Ly);
+                  for (int k = 0; k < 2; k++)
+                  {
+                     double s = 0.0;
+                     for (int by = 0; by < 3; by++) { for (int bx = 0; bx < 3; bx++) { s += Ly[by] * Lx[bx] * Xp[k * 9 + bx + 3 * by]; } }
+                     X[(ch * 2 + k) * 9 + ax + 3 * ay] = s;
+                  }
+               }
+            }
+         }
+      }
+   }
+   m.nv = nv;
+   m.ev.swap(ev);
+   m.X.swap(X);
+}
+} // namespace
+
+// A case on the quadrilateral mesh of a file (cfg.mesh_file), one rank: the steps of build_case_2d element by element -- CFL step from
+// the centre Jacobian, remap displacement of every node copy (equal positions give equal displacements), nodal initial condition at the
+// closed-uniform points, sub-mesh velocity for lo 4 (zero at the dofs on the domain boundary in remap mode) -- and the tables of
+// quad_topology in the place of the 3 x 3 stencil.  The bounding box is taken over the element nodes.
+static std::string build_case_file(const CaseConfig &cfg, CaseData &out, bool &opened)
+{
+   QuadMesh mesh;
+   std::string err;
+   opened = read_quad_mesh(cfg.mesh_file, mesh, err);
+   if (!opened) { return "cannot open"; }
+   if (!err.empty()) { return err; }
+   if (cfg.order < 1 || cfg.order > 6) { return "order must be in 1..6"; }
+   if (cfg.px != 1 || cfg.py != 1 || cfg.pz != 1 || cfg.rank != 0 || cfg.self_wrap != 0) { return "partitions: an unstructured mesh file runs on one rank"; }
+   if (cfg.rs_extra[0] || cfg.rs_extra[1] || cfg.rs_extra[2]) { return "unstructured mesh file: no rs_extra"; }
+   if (cfg.lo_type < 1 || cfg.lo_type > 5) { return "lo_type must be 1, 2, 3, 4 or 5"; }
+   if (cfg.rs < 0 || cfg.rs > 8) { return "bad rs"; }
+   if (const std::string e = check_problem(cfg.problem); !e.empty()) { return e; }
+   const std::string who = "mesh file '" + cfg.mesh_file + "': ";
+   out = CaseData();
+   // (the coarse mesh is checked too: the refinement keys the new vertices by the vertex pairs of the edges)
+   for (int l = 0; l <= cfg.rs; l++)
+   {
+      if (l > 0) { refine_quad_mesh(mesh); }
+      if (l == 0 || l == cfg.rs)
+      {
+         const std::string e = quad_topology(mesh.ne(), mesh.ev.data(), out.face_nbr, out.face_code, out.corner_ptr, out.corner_elems);
+         if (!e.empty()) { return who + e; }
+      }
+   }
+   const int ne = mesh.ne(), p = cfg.order, D = p + 1, problem = cfg.problem;
+   out.dim = 2;
+   out.unstructured = true;
+   out.order = p;
+   out.exec_mode = problem < 10 ? 0 : 1;
+   out.ndof = D * D;
+   out.ne_global = ne;
+   out.ne_owned = ne;
+   out.elem_vertices = mesh.ev;
+   out.x0 = mesh.X;
+   out.periodic = std::find(out.face_nbr.begin(), out.face_nbr.end(), -1) == out.face_nbr.end();
+   for (int d = 0; d < 3; d++)
+   {
+      out.n[d] = out.nl[d] = d == 0 ? ne : 1;
+      out.lo[d] = 0;
+      out.bb_min[d] = out.bb_max[d] = 0.0;
+   }
+   for (int c = 0; c < 2; c++) { out.bb_min[c] = INFINITY; out.bb_max[c] = -INFINITY; }
+   for (int e = 0; e < ne; e++)
+   {
+      for (int c = 0; c < 2; c++)
+      {
+         for (int a = 0; a < 9; a++)
+         {
+            out.bb_min[c] = std::fmin(out.bb_min[c], out.x0[((size_t)e * 2 + c) * 9 + a]);
+            out.bb_max[c] = std::fmax(out.bb_max[c], out.x0[((size_t)e * 2 + c) * 9 + a]);
+         }
+      }
+   }
+   const double *bmin = out.bb_min, *bmax = out.bb_max;
+   // orientation, and the time step (remhos.cpp:538-553): 0.25 |det J(centre)|^(1/2) / |v(centre)|
+   double dt = cfg.dt < 0.0 ? INFINITY : cfg.dt;
+   for (int e = 0; e < ne; e++)
+   {
+      const double *X = &out.x0[(size_t)e * 18];
+      // J(centre) of the Q2 map: differences of the mid-edge nodes
+      const double det = (X[5] - X[3]) * (X[9 + 7] - X[9 + 1]) - (X[7] - X[1]) * (X[9 + 5] - X[9 + 3]);
+      if (!(det > 0.0))
+      {
+         return who + "element " + std::to_string(e) + " is clockwise or degenerate (det J = " + std::to_string(det) + " at its centre): the elements must be counter-clockwise";
+      }
+      if (cfg.dt < 0.0)
+      {
+         const double xc[2] = {X[4], X[9 + 4]};
+         double v[2];
+         velocity_function_2d(problem, bmin, bmax, xc, v);
+         dt = std::fmin(dt, 0.25 * std::sqrt(std::fabs(det)) / std::sqrt(v[0] * v[0] + v[1] * v[1] + 1e-14));
+      }
+   }
+   out.dt = dt;
+   const bool remap = out.exec_mode == 1;
+   out.vel.resize((size_t)ne * 18);
+   out.u0.resize((size_t)ne * out.ndof);
+   out.s0.resize((size_t)ne * out.ndof);
+   const bool lo4 = cfg.lo_type == 4;
+   if (lo4) { out.subcell_vel.assign((size_t)ne * 2 * out.ndof, 0.0); }
+   out.owned_gid.resize(ne);
+   out.stencil27.assign((size_t)ne * 9, -1);
+   // vertices on the domain boundary: a dof of the sub-mesh there does not move in remap mode (remhos.cpp:837-853), whether its
+   // element has a boundary face or only touches the boundary with a corner
+   static const int FC[4][2] = {{0, 2}, {1, 3}, {0, 1}, {2, 3}};
+   std::map<int, bool> bdr_vertex;
+   for (int e = 0; e < ne; e++)
+   {
+      for (int f = 0; f < 4; f++)
+      {
+         if (out.face_nbr[(size_t)e * 4 + f] < 0) { for (int k = 0; k < 2; k++) { bdr_vertex[mesh.ev[(size_t)e * 4 + FC[f][k]]] = true; } }
+      }
+   }
+   std::vector<double> Lcu(3 * D);
+   for (int i = 0; i < D; i++) { lag2((double)i / p, &Lcu[3 * i]); }
+   for (int e = 0; e < ne; e++)
+   {
+      out.owned_gid[e] = e;
+      out.stencil27[(size_t)e * 9 + 4] = e;
+      const double *ex0 = &out.x0[(size_t)e * 18];
+      double *ev = &out.vel[(size_t)e * 18];
+      for (int a = 0; a < 9; a++)
+      {
+         const double x0[2] = {ex0[a], ex0[9 + a]};
+         double x[2] = {x0[0], x0[1]}, v[2];
+         velocity_function_2d(problem, bmin, bmax, x, v);
+         if (remap)
+         {
+            double t = 0.0; // (the reference's order: t advances BEFORE min(dt, t_final - t) is taken)
+            while (t < cfg.t_final)
+            {
+               t += dt;
+               const double hh = std::min(dt, cfg.t_final - t);
+               for (int c = 0; c < 2; c++) { x[c] = x[c] + hh * v[c]; }
+               velocity_function_2d(problem, bmin, bmax, x, v);
+            }
+            for (int c = 0; c < 2; c++) { v[c] = x[c] - x0[c]; }
+         }
+         for (int c = 0; c < 2; c++) { ev[c * 9 + a] = v[c]; }
+      }
+      for (int iy = 0; iy < D; iy++)
+      {
+         for (int ix = 0; ix < D; ix++)
+         {
+            double x[3] = {0, 0, 0};
+            for (int ay = 0; ay < 3; ay++)
+            {
+               for (int ax = 0; ax < 3; ax++)
+               {
+                  const double w = Lcu[3 * ix + ax] * Lcu[3 * iy + ay];
+                  for (int c = 0; c < 2; c++) { x[c] += w * ex0[c * 9 + ax + 3 * ay]; }
+               }
+            }
+            const int i = ix + D * iy;
+            out.u0[(size_t)e * out.ndof + i] = u0_function_2d(problem, bmin, bmax, x); // remhos.cpp:878-884
+            out.s0[(size_t)e * out.ndof + i] = s0_function(x);
+            if (lo4)
+            {
+               double v[2];
+               velocity_function_2d(problem, bmin, bmax, x, v);
+               bool bdr = false;
+               if (remap)
+               {
+                  const int *fn = &out.face_nbr[(size_t)e * 4];
+                  bdr = (fn[0] < 0 && ix == 0) || (fn[1] < 0 && ix == p) || (fn[2] < 0 && iy == 0) || (fn[3] < 0 && iy == p);
+                  if ((ix == 0 || ix == p) && (iy == 0 || iy == p))
+                  {
+                     bdr = bdr || bdr_vertex.count(mesh.ev[(size_t)e * 4 + (ix == p ? 1 : 0) + (iy == p ? 2 : 0)]) != 0;
+                  }
+               }
+               for (int c = 0; c < 2; c++) { out.subcell_vel[((size_t)e * 2 + c) * out.ndof + i] = bdr ? 0.0 : v[c]; }
+            }
+         }
+      }
+   }
+   return "";
+}
+
 std::string build_case(const CaseConfig &cfg, CaseData &out)
 {
    if (cfg.mesh == "periodic-segment") { return build_case_1d(cfg, out); }
    if (cfg.mesh == "inline-quad" || cfg.mesh == "periodic-square") { return build_case_2d(cfg, out); }
    MeshDef md;
-   if (!lookup_mesh(cfg.mesh, md)) { return "unknown lattice mesh '" + cfg.mesh + "' (periodic-cube, cube01_hex)"; }
+   if (!lookup_mesh(cfg.mesh, md))
+   {
+      // not built in: the quadrilateral mesh of a file, if one is named and can be read
+      bool opened = false;
+      if (!cfg.mesh_file.empty())
+      {
+         const std::string e = build_case_file(cfg, out, opened);
+         if (opened) { return e; }
+      }
+      return "unknown lattice mesh '" + cfg.mesh + "' (periodic-cube, cube01_hex)" + (cfg.mesh_file.empty() ? "" : ", and no readable mesh file at '" + cfg.mesh_file + "'");
+   }
    if (cfg.order < 1 || cfg.order > 6) { return "order must be in 1..6"; }
    if (cfg.px < 1 || cfg.py < 1 || cfg.pz < 1) { return "bad partition"; }
    const int nranks = cfg.px * cfg.py * cfg.pz;
@@ -998,6 +1505,7 @@ std::string lp_error_sums(const CaseData &d, int problem, double t_exact, const 
    const int prob = problem % 10;
    if (prob != 0 && prob != 4) { return "no exact solution is defined for this problem (4: rotation, 0: translation)"; }
    if (prob == 0 && !d.periodic) { return "the translated exact field is defined on the periodic meshes"; }
+   if (d.unstructured) { return "error norms are not built for unstructured mesh files (the periodic wrap of the exact field is a lattice's)"; }
    if (d.exec_mode != 0) { return "error norms are for the transport problems"; }
    const int p = d.order, D = p + 1, nq = p + 2; // order 2 p + 3 -> p + 2 points per direction
    std::vector<double> xq, wq;

@@ -28,6 +28,9 @@ struct CaseConfig
    // bit.  Needs a periodic mesh, one block in that direction and at least three elements across it.  0: off.
    int self_wrap = 0;
    int tile_rows = 0; // element numbering: 0 lattice order; T > 0: y-strips of T rows, z before y inside a strip (rmh_driver.h)
+   // Path of an "MFEM mesh v1.0" file of quadrilaterals, read when `mesh` is not one of the built-in lattice names (then it is
+   // ignored): the unstructured 2-D meshes of the reference's data/ (star-q2, periodic-hexagon).  Empty: built-in names only.
+   std::string mesh_file;
 };
 
 // neighbour rank in the halo exchange: which owned elements it needs, which ghost slots it fills
@@ -61,7 +64,19 @@ struct CaseData
    std::vector<int> stencil27;      // [ne_owned][27]
    std::vector<long long> owned_gid, ghost_gid;
    std::vector<Peer> peers;
+   // dim = 2 from a mesh file (CaseConfig::mesh_file): the tables of rmh_build_tables_quad beside face_nbr; stencil27 [ne][9] then
+   // holds the element itself in the centre and -1 elsewhere, n / lo / nl are (ne, 1, 1)
+   bool unstructured = false;
+   std::vector<int> elem_vertices;       // [ne][4] vertex ids, corner k = kx + 2 ky
+   std::vector<unsigned char> face_code; // [ne][4]
+   std::vector<int> corner_ptr, corner_elems; // CSR [4 ne + 1], [corner_ptr.back()]
 };
+
+// is `name` one of the lattice meshes the case builder has built in?
+bool is_builtin_mesh(const std::string &name);
+// include/rmh.h, rmh_build_tables_quad: "" or why the mesh is refused
+std::string quad_topology(int ne, const int *elem_vertices, std::vector<int> &face_nbr, std::vector<unsigned char> &face_code,
+                          std::vector<int> &corner_ptr, std::vector<int> &corner_elems);
 
 // problem definitions (remhos.cpp:2001-2120, 2201-2355)
 void velocity_function(int problem, const double *bb_min, const double *bb_max, const double x[3], double v[3]);
