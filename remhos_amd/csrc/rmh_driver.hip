@@ -1,12 +1,18 @@
-// Host classes of include/remhos_amd/solvers.hpp and the single-GPU time loop rmhd_run().
+// The host driver (include/rmh_driver.h), in this order: the classes of include/remhos_amd/solvers.hpp (Vector, the HO / LO / FCT /
+// monolithic solvers, AdvectionOperator, the ODE solvers), which forward to the C ABI; then, in the anonymous namespace, the option
+// refusals (validate_config, check_case), the set-up pieces both time loops share (layout, exchange plan, RCCL id rendezvous, step
+// clock, result tail), one block through the solver classes (BlockRun: rmhd_run, rmhd_run_state, rmhd_run_rank) and the blocks of
+// a partition through the one-kernel stage (rmhd_run_partitioned).
 #include "../../include/remhos_amd/solvers.hpp"
 #include "../../include/rmh_driver.h"
 #include "rmh_host.hpp"
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <chrono>
 #include <ctime>
+#include <memory>
 #include <sys/stat.h>
 #include <unistd.h>
 #include <cmath>
@@ -276,107 +282,6 @@ void MonoRDSolver::CalcSolution(const Vector &u, Vector &du) const
    RMH_CALL(rmh_mono_rd(pfes.Ctx(), u.Read(), dofs.xi_min.Read(), dofs.xi_max.Read(), scale.Read(), mass_lim ? 1 : 0, du.Write()));
 }
 
-// -mono of rmhd_config: 0 on success, else the message is in g_driver_error
-static int check_mono_type(const rmhd_config *cfg, bool partitioned)
-{
-   const int mono = cfg->mono_type;
-   if (mono == 0) { return 0; }
-   if (mono == 2) { g_driver_error = "mono_type 2 (-mono 2): the subcell variant of the monolithic RD solver (ResDistMonoSubcell) is not built"; return -1; }
-   if (mono != 1) { g_driver_error = "mono_type must be 0 (off) or 1 (-mono 1, MonoRDSolver): got " + std::to_string(mono); return -1; }
-   if (partitioned || cfg->px * cfg->py * cfg->pz > 1) { g_driver_error = "mono_type 1 (-mono 1): partitioned runs are not built for the monolithic RD solver (one block, rmhd_run with fused = 0)"; return -1; }
-   if (cfg->self_wrap) { g_driver_error = "mono_type 1 (-mono 1): a self-wrapped block (self_wrap) has ghost elements, which rmh_mono_rd does not take"; return -1; }
-   if (cfg->fused) { g_driver_error = "mono_type 1 (-mono 1): the fused limiter and the one-kernel stage are the HO / LO / FCT split the monolithic solver replaces (fused must be 0)"; return -1; }
-   if (cfg->ps) { g_driver_error = "mono_type 1 (-mono 1) with -ps: product remap (ps) is not built for the monolithic RD solver"; return -1; }
-   if (cfg->ode_solver != 0 && cfg->ode_solver != 3) { g_driver_error = "mono_type 1 (-mono 1): runs through RK3 SSP (-s 3); the IDP solvers limit a rate the monolithic solver does not have"; return -1; }
-   if (cfg->dt_control) { g_driver_error = "mono_type 1 (-mono 1) with -dtc: the time step estimate is formed from the LO solution, which the monolithic solver does not have"; return -1; }
-   return 0;
-}
-
-// -fct of rmhd_config: what the entry points below accept (0 on success, else the message is in g_driver_error)
-static int check_fct_type(const rmhd_config *cfg, bool partitioned)
-{
-   const int fct = cfg->fct_type;
-   // -ho: 0 means 3; no other value may fall through to the local inverse
-   if (cfg->ho_type < 0 || cfg->ho_type > 3) { g_driver_error = "ho_type must be 1 (Neumann iteration), 2 (CG) or 3 (local inverse; 0 means 3): got " + std::to_string(cfg->ho_type); return -1; }
-   if (cfg->ho_type == 1)
-   {
-      // NeumannHOSolver (-ho 1) runs through the granular solver sequence on one block: its stopping test is a global norm
-      if (partitioned || cfg->px * cfg->py * cfg->pz > 1) { g_driver_error = "ho_type 1 (-ho 1): partitioned runs are not built for the Neumann HO solver (one block, rmhd_run with fused = 0)"; return -1; }
-      if (cfg->self_wrap) { g_driver_error = "ho_type 1 (-ho 1): a self-wrapped block (self_wrap) has ghost elements, which rmh_ho_neumann does not take"; return -1; }
-      if (cfg->fused) { g_driver_error = "ho_type 1 (-ho 1): the one-kernel stage has the local inverse built in (fused must be 0)"; return -1; }
-      if (cfg->pa) { g_driver_error = "ho_type 1 (-ho 1) with -pa: PA for DG is not supported for Neummann Solver"; return -1; } // remhos_ho.cpp:138-139
-      if (cfg->ps) { g_driver_error = "ho_type 1 (-ho 1) with -ps: product remap (ps) is not built for the Neumann HO solver"; return -1; }
-   }
-   if (fct != 0 && fct != 1 && fct != 2 && fct != 4) { g_driver_error = "fct_type must be 1 (flux-based FCT), 2 (clip + scale; 0 means 2) or 4 (element FCT projection)"; return -1; }
-   if (fct == 1 || cfg->lo_type == 1 || cfg->lo_type == 2)
-   {
-      // DiscreteUpwind (-lo 1, preconditioned: -lo 2) and FluxBasedFCT (-fct 1) run through the granular solver sequence on one block
-      const char *who = fct == 1 ? "fct_type 1" : (cfg->lo_type == 2 ? "lo_type 2" : "lo_type 1");
-      if (partitioned || cfg->px * cfg->py * cfg->pz > 1) { g_driver_error = std::string(who) + ": partitioned runs are not built for the DiscreteUpwind / FluxBasedFCT solvers (one block, rmhd_run with fused = 0)"; return -1; }
-      if (cfg->fused) { g_driver_error = std::string(who) + ": the fused limiter and the one-kernel stage have their LO solver and clip + scale built in (fused must be 0)"; return -1; }
-      if (cfg->ps) { g_driver_error = std::string(who) + ": product remap (ps) is not implemented for the DiscreteUpwind / FluxBasedFCT solvers"; return -1; }
-      if (fct == 1 && cfg->pa) { g_driver_error = "Flux-based FCT and PA are incompatible."; return -1; } // remhos.cpp:1088
-      if (fct == 1 && cfg->self_wrap) { g_driver_error = "fct_type 1: a self-wrapped block has ghost elements, which rmh_fct_fluxbased does not take"; return -1; }
-   }
-   if (fct != 4) { return 0; }
-   if (partitioned) { g_driver_error = "rmhd_run_partitioned runs the one-kernel stage, which has clip + scale built in: fct_type 4 runs through rmhd_run / rmhd_run_rank with fused = 0"; return -1; }
-   if (cfg->fused) { g_driver_error = "fct_type 4: the fused limiter and the one-kernel stage have clip + scale built in (fused must be 0)"; return -1; }
-   if (cfg->ps) { g_driver_error = "fct_type 4: product remap (ps) is not implemented for the element FCT projection"; return -1; }
-   return 0;
-}
-
-// dim = 1 (-m data/periodic-segment.mesh): what a segment run takes -- -ho 2|3, -lo 3|4|5, -fct 2, -s 3, one block.  Every
-// other option is refused here, before a device context exists (0 on success, else the message is in g_driver_error)
-static bool is_segment_mesh(const rmhd_config *cfg) { return std::strncmp(cfg->mesh, "periodic-segment", sizeof(cfg->mesh)) == 0; }
-static int check_dim1(const rmhd_config *cfg, bool partitioned)
-{
-   const char *why = nullptr;
-   const int ode = cfg->ode_solver, lo = cfg->lo_type, fct = cfg->fct_type;
-   if (cfg->ps) { why = "ps (-ps): product remap"; }
-   else if (ode != 0 && ode != 3) { why = "ode_solver (-s 11|12|13): the IDP solvers"; }
-   else if (cfg->ho_type == 1) { why = "ho_type 1 (-ho 1): the Neumann HO solver"; }
-   else if (lo == 1 || lo == 2) { why = "lo_type 1|2 (-lo 1|2): the DiscreteUpwind LO solvers"; }
-   else if (fct == 1 || fct == 4) { why = "fct_type 1|4 (-fct 1|4): the flux-based and element-projection FCT solvers"; }
-   else if (cfg->mono_type) { why = "mono_type (-mono): the monolithic RD solver"; }
-   else if (partitioned || cfg->px > 1 || cfg->py > 1 || cfg->pz > 1 || cfg->rank != 0) { why = "partitions (px, py, pz, rank): box-partitioned runs"; }
-   else if (cfg->self_wrap) { why = "self_wrap: the self-wrapped halo"; }
-   else if (cfg->save) { why = "save (-save): the MFEM mesh / field writer"; }
-   if (!why) { return 0; }
-   g_driver_error = std::string(why) + " is not available for dim = 1 (periodic-segment: -ho 2|3, -lo 3|4|5, -fct 2, -s 3, one block)";
-   return -1;
-}
-
-// An unstructured quadrilateral mesh from a file (rmhd_config.mesh_file; data/star-q2.mesh, data/periodic-hexagon.mesh): the name is
-// none of the built-in lattices and the file can be opened.  (Neither: the case builder answers "unknown lattice mesh".)  Such a run
-// takes -ho 2|3 [-pa], -lo 3|4|5, -fct 2, -bt, -dtc, -vb, -s 3 on one block through the granular solver sequence; every other option
-// is refused here, before a device context exists (0 on success, else the message is in g_driver_error)
-static bool is_file_mesh(const rmhd_config *cfg)
-{
-   if (is_builtin_mesh(std::string(cfg->mesh, strnlen(cfg->mesh, sizeof(cfg->mesh)))) || !cfg->mesh_file[0]) { return false; }
-   if (strnlen(cfg->mesh_file, sizeof(cfg->mesh_file)) == sizeof(cfg->mesh_file)) { return false; }
-   FILE *f = std::fopen(cfg->mesh_file, "r");
-   if (f) { std::fclose(f); }
-   return f != nullptr;
-}
-static int check_unstructured(const rmhd_config *cfg, bool partitioned)
-{
-   const char *why = nullptr;
-   const int ode = cfg->ode_solver, lo = cfg->lo_type, fct = cfg->fct_type;
-   if (partitioned || cfg->px > 1 || cfg->py > 1 || cfg->pz > 1 || cfg->rank != 0) { why = "partitions (px, py, pz, rank): box-partitioned runs are"; }
-   else if (cfg->mono_type) { why = "mono_type (-mono): the monolithic RD solver is"; }
-   else if (cfg->fused) { why = "fused = 1: the fused limiter and the one-kernel stage (they read the neighbour tables with the lattice rule) are"; }
-   else if (cfg->ho_type == 1) { why = "ho_type 1 (-ho 1): the Neumann HO solver is"; }
-   else if (lo == 1 || lo == 2) { why = "lo_type 1|2 (-lo 1|2): the DiscreteUpwind LO solvers are"; }
-   else if (fct == 1) { why = "fct_type 1 (-fct 1): the flux-based FCT solver is"; }
-   else if (fct == 4) { why = "fct_type 4 (-fct 4): the element FCT projection is"; }
-   else if (cfg->ps) { why = "ps (-ps): product remap is"; }
-   else if (ode != 0 && ode != 3) { why = "ode_solver (-s 11|12|13): the IDP solvers are"; }
-   else if (cfg->self_wrap) { why = "self_wrap: the self-wrapped halo is"; }
-   else if (cfg->save) { why = "save (-save): the MFEM mesh / field writer is"; }
-   if (!why) { return 0; }
-   g_driver_error = std::string(why) + " not available on an unstructured mesh file (-ho 2|3 [-pa], -lo 3|4|5, -fct 2, -bt 0|1, -dtc 0|1, -vb, -s 3, one block, fused = 0)";
-   return -1;
-}
 
 // remhos.cpp:1557-1594
 static void report_violation(const rmh_violation &v, const std::string &info)
@@ -680,23 +585,22 @@ void RK3SSPSolver::Init(LimitedTimeDependentOperator &op)
    y.SetSize(op.Height());
    k.SetSize(op.Height());
 }
+// The schedule of the method, read by RK3SSPSolver::Step and by both one-kernel stage loops below: stage i takes its input x_i
+// (x_0 = x) at the time t + c dt and leaves  a x + b (x_i + dt f(t + c dt, x_i))  -- x_1, x_2 and the new x.
+struct RK3SSPStage { double c, a, b; };
+constexpr RK3SSPStage RK3SSP[3] = {{0., 0., 1.}, {1., 3. / 4, 1. / 4}, {1. / 2, 1. / 3, 2. / 3}};
+
 void RK3SSPSolver::Step(Vector &x, real_t &t, real_t &dt)
 {
-   // x0 = x, t0 = t, k0 = dt*f(t0, x0)
-   f->SetTime(t);
-   f->Mult(x, k);
-   // x1 = x + k0, t1 = t + dt, k1 = dt*f(t1, x1)
-   add(x, dt, k, y);
-   f->SetTime(t + dt);
-   f->Mult(y, k);
-   // x2 = 3/4*x + 1/4*(x1 + k1), t2 = t + 1/2*dt, k2 = dt*f(t2, x2)
-   add(y, dt, k, y);
-   add(3. / 4, x, 1. / 4, y, y);
-   f->SetTime(t + dt / 2);
-   f->Mult(y, k);
-   // x3 = 1/3*x + 2/3*(x2 + k2), t3 = t + dt
-   add(y, dt, k, y);
-   add(1. / 3, x, 2. / 3, y, x);
+   for (int i = 0; i < 3; i++)
+   {
+      const RK3SSPStage &st = RK3SSP[i];
+      const Vector &xi = (i == 0) ? x : y;
+      f->SetTime(t + st.c * dt);
+      f->Mult(xi, k);
+      add(xi, dt, k, y);
+      if (i > 0) { add(st.a, x, st.b, y, (i == 2) ? x : y); } // (stage 0: a = 0, b = 1)
+   }
    t += dt;
 }
 
@@ -706,524 +610,195 @@ using namespace remhos;
 
 namespace
 {
-bool read_or_write_id(const char *path, bool writer, char id[128]); // (below, with rmhd_run_partitioned)
+int refuse(const std::string &why) { g_driver_error = why; return -1; }
+
+// ---- option refusals ---------------------------------------------------------------------------------------------------
+// Every option set the entry points refuse is refused in one of two places: validate_config (what rmhd_config alone decides, before
+// a case is built) and check_case (what needs the built CaseData: dimension, order, exec_mode).  A new rule goes into the one that
+// can decide it, at the place its precedence asks for: the FIRST rule that fails is the one reported, and
+// tests/golden/driver_refusals.json pins which.
+bool is_segment_mesh(const rmhd_config &cfg) { return std::strncmp(cfg.mesh, "periodic-segment", sizeof(cfg.mesh)) == 0; }
+
+// An unstructured quadrilateral mesh from a file (rmhd_config.mesh_file; data/star-q2.mesh, data/periodic-hexagon.mesh): the name is
+// none of the built-in lattices and the file can be opened.  (Neither: the case builder answers "unknown lattice mesh".)
+bool is_file_mesh(const rmhd_config &cfg)
+{
+   if (is_builtin_mesh(std::string(cfg.mesh, strnlen(cfg.mesh, sizeof(cfg.mesh)))) || !cfg.mesh_file[0]) { return false; }
+   if (strnlen(cfg.mesh_file, sizeof(cfg.mesh_file)) == sizeof(cfg.mesh_file)) { return false; }
+   FILE *f = std::fopen(cfg.mesh_file, "r");
+   if (f) { std::fclose(f); }
+   return f != nullptr;
 }
 
-extern "C" int rmhd_run(const rmhd_config *cfg, rmhd_result *res) { return rmhd_run_rank(cfg, nullptr, 0, res, nullptr, nullptr); }
-
-extern "C" int rmhd_run_state(const rmhd_config *cfg, rmhd_result *res, double *u_final, double *us_final)
+struct Validated
 {
-   return rmhd_run_rank(cfg, nullptr, 0, res, u_final, us_final);
-}
+   std::string refusal; // empty: `cfg` is the effective config
+   rmhd_config cfg;     // the caller's, with pa cleared on a segment mesh and -ho / -lo / -fct / -pa at their defaults beside -mono
+};
 
-extern "C" int rmhd_run_rank(const rmhd_config *cfg, const char *comm_id_file, int device, rmhd_result *res, double *u_final,
-                             double *us_final)
+// What the entry points accept of rmhd_config, before a device context exists.  partitioned_entry: rmhd_run_partitioned; id_file:
+// the caller names an RCCL id file (one process per block).  The groups, in the order they are asked: dim = 1, a mesh file,
+// -mono, -ho / -lo / -fct, the entry point's own rule.
+Validated validate_config(const rmhd_config &in, bool partitioned_entry, bool id_file)
 {
-   if (!cfg || !res) { g_driver_error = "null argument"; return -1; }
-   std::memset(res, 0, sizeof(*res));
-   rmhd_config seg_cfg;
+   Validated v{std::string(), in};
+   rmhd_config &cfg = v.cfg;
+   std::string &no = v.refusal;
+   const char *why = nullptr;
+   const int ode = cfg.ode_solver;
+   // "is this run partitioned" has two spellings, and they stay: the second also refuses rank != 0 on one block, which the first
+   // leaves to the case builder ("bad rank")
+   const bool many_blocks = partitioned_entry || cfg.px * cfg.py * cfg.pz > 1;
+   const bool many_blocks_or_rank = partitioned_entry || cfg.px > 1 || cfg.py > 1 || cfg.pz > 1 || cfg.rank != 0;
+
+   // dim = 1 (-m data/periodic-segment.mesh): what a segment run takes -- -ho 2|3, -lo 3|4|5, -fct 2, -s 3, one block
    if (is_segment_mesh(cfg))
    {
-      if (check_dim1(cfg, false) != 0) { return -1; }
-      if (cfg->pa)
+      const int lo = cfg.lo_type, fct = cfg.fct_type;
+      if (cfg.ps) { why = "ps (-ps): product remap"; }
+      else if (ode != 0 && ode != 3) { why = "ode_solver (-s 11|12|13): the IDP solvers"; }
+      else if (cfg.ho_type == 1) { why = "ho_type 1 (-ho 1): the Neumann HO solver"; }
+      else if (lo == 1 || lo == 2) { why = "lo_type 1|2 (-lo 1|2): the DiscreteUpwind LO solvers"; }
+      else if (fct == 1 || fct == 4) { why = "fct_type 1|4 (-fct 1|4): the flux-based and element-projection FCT solvers"; }
+      else if (cfg.mono_type) { why = "mono_type (-mono): the monolithic RD solver"; }
+      else if (many_blocks_or_rank) { why = "partitions (px, py, pz, rank): box-partitioned runs"; }
+      else if (cfg.self_wrap) { why = "self_wrap: the self-wrapped halo"; }
+      else if (cfg.save) { why = "save (-save): the MFEM mesh / field writer"; }
+      if (why) { no = std::string(why) + " is not available for dim = 1 (periodic-segment: -ho 2|3, -lo 3|4|5, -fct 2, -s 3, one block)"; return v; }
+      if (cfg.pa)
       {
          // remhos.cpp:474-480; the element mass solve of a segment is exact either way (rmh_1d.hpp)
          std::printf("Disabling PA / FA for 1D.\n");
          std::fflush(stdout);
-         seg_cfg = *cfg;
-         seg_cfg.pa = 0;
-         cfg = &seg_cfg;
+         cfg.pa = 0;
       }
    }
-   if (is_file_mesh(cfg) && check_unstructured(cfg, false) != 0) { return -1; }
-   if (check_mono_type(cfg, false) != 0) { return -1; }
-   rmhd_config mono_cfg;
-   if (cfg->mono_type)
+   // a mesh file takes -ho 2|3 [-pa], -lo 3|4|5, -fct 2, -bt, -dtc, -vb, -s 3 on one block through the granular solver sequence
+   if (is_file_mesh(cfg))
    {
+      const int lo = cfg.lo_type, fct = cfg.fct_type;
+      if (many_blocks_or_rank) { why = "partitions (px, py, pz, rank): box-partitioned runs are"; }
+      else if (cfg.mono_type) { why = "mono_type (-mono): the monolithic RD solver is"; }
+      else if (cfg.fused) { why = "fused = 1: the fused limiter and the one-kernel stage (they read the neighbour tables with the lattice rule) are"; }
+      else if (cfg.ho_type == 1) { why = "ho_type 1 (-ho 1): the Neumann HO solver is"; }
+      else if (lo == 1 || lo == 2) { why = "lo_type 1|2 (-lo 1|2): the DiscreteUpwind LO solvers are"; }
+      else if (fct == 1) { why = "fct_type 1 (-fct 1): the flux-based FCT solver is"; }
+      else if (fct == 4) { why = "fct_type 4 (-fct 4): the element FCT projection is"; }
+      else if (cfg.ps) { why = "ps (-ps): product remap is"; }
+      else if (ode != 0 && ode != 3) { why = "ode_solver (-s 11|12|13): the IDP solvers are"; }
+      else if (cfg.self_wrap) { why = "self_wrap: the self-wrapped halo is"; }
+      else if (cfg.save) { why = "save (-save): the MFEM mesh / field writer is"; }
+      if (why) { no = std::string(why) + " not available on an unstructured mesh file (-ho 2|3 [-pa], -lo 3|4|5, -fct 2, -bt 0|1, -dtc 0|1, -vb, -s 3, one block, fused = 0)"; return v; }
+   }
+   if (const int mono = cfg.mono_type)
+   {
+      if (mono == 2) { no = "mono_type 2 (-mono 2): the subcell variant of the monolithic RD solver (ResDistMonoSubcell) is not built"; }
+      else if (mono != 1) { no = "mono_type must be 0 (off) or 1 (-mono 1, MonoRDSolver): got " + std::to_string(mono); }
+      else if (many_blocks) { no = "mono_type 1 (-mono 1): partitioned runs are not built for the monolithic RD solver (one block, rmhd_run with fused = 0)"; }
+      else if (cfg.self_wrap) { no = "mono_type 1 (-mono 1): a self-wrapped block (self_wrap) has ghost elements, which rmh_mono_rd does not take"; }
+      else if (cfg.fused) { no = "mono_type 1 (-mono 1): the fused limiter and the one-kernel stage are the HO / LO / FCT split the monolithic solver replaces (fused must be 0)"; }
+      else if (cfg.ps) { no = "mono_type 1 (-mono 1) with -ps: product remap (ps) is not built for the monolithic RD solver"; }
+      else if (ode != 0 && ode != 3) { no = "mono_type 1 (-mono 1): runs through RK3 SSP (-s 3); the IDP solvers limit a rate the monolithic solver does not have"; }
+      else if (cfg.dt_control) { no = "mono_type 1 (-mono 1) with -dtc: the time step estimate is formed from the LO solution, which the monolithic solver does not have"; }
+      if (!no.empty()) { return v; }
       // -ho, -lo and -fct are ignored beside -mono, as in the reference (remhos.cpp:1687): they take their defaults here
-      mono_cfg = *cfg;
-      mono_cfg.ho_type = 0;
-      mono_cfg.lo_type = 5;
-      mono_cfg.fct_type = 0;
-      mono_cfg.pa = 0;
-      cfg = &mono_cfg;
+      cfg.ho_type = 0; cfg.lo_type = 5; cfg.fct_type = 0; cfg.pa = 0;
    }
-   if (check_fct_type(cfg, false) != 0) { return -1; }
-   CaseConfig cc = to_config(*cfg);
-   const int nranks = cc.px * cc.py * cc.pz;
-   const bool rccl_ranks = comm_id_file && comm_id_file[0];
-   if (nranks != 1 && !rccl_ranks)
+   // -ho: 0 means 3; no other value may fall through to the local inverse
+   if (cfg.ho_type < 0 || cfg.ho_type > 3) { no = "ho_type must be 1 (Neumann iteration), 2 (CG) or 3 (local inverse; 0 means 3): got " + std::to_string(cfg.ho_type); return v; }
+   if (cfg.ho_type == 1)
    {
-      g_driver_error = "rmhd_run drives one block; box-partitioned runs go through rmhd_run_partitioned, or through "
-                       "rmhd_run_rank with one process per block";
-      return -1;
+      // NeumannHOSolver (-ho 1) runs through the granular solver sequence on one block: its stopping test is a global norm
+      if (many_blocks) { no = "ho_type 1 (-ho 1): partitioned runs are not built for the Neumann HO solver (one block, rmhd_run with fused = 0)"; }
+      else if (cfg.self_wrap) { no = "ho_type 1 (-ho 1): a self-wrapped block (self_wrap) has ghost elements, which rmh_ho_neumann does not take"; }
+      else if (cfg.fused) { no = "ho_type 1 (-ho 1): the one-kernel stage has the local inverse built in (fused must be 0)"; }
+      else if (cfg.pa) { no = "ho_type 1 (-ho 1) with -pa: PA for DG is not supported for Neummann Solver"; } // remhos_ho.cpp:138-139
+      else if (cfg.ps) { no = "ho_type 1 (-ho 1) with -ps: product remap (ps) is not built for the Neumann HO solver"; }
+      if (!no.empty()) { return v; }
    }
-   CaseData cd;
-   const std::string err = build_case(cc, cd);
-   if (!err.empty()) { g_driver_error = err; return -1; }
-   if (cc.lo_type == 2 && cd.dim == 3 && cd.order >= 4)
+   const int fct = cfg.fct_type;
+   if (fct != 0 && fct != 1 && fct != 2 && fct != 4) { no = "fct_type must be 1 (flux-based FCT), 2 (clip + scale; 0 means 2) or 4 (element FCT projection)"; return v; }
+   if (fct == 1 || cfg.lo_type == 1 || cfg.lo_type == 2)
    {
-      g_driver_error = "lo_type 2 (-lo 2): order " + std::to_string(cd.order) + " in 3-D is not supported: the element's dense matrices must fit the LDS (orders 1 to 3 in 3-D, 1 to 6 in 2-D)";
-      return -1;
+      // DiscreteUpwind (-lo 1, preconditioned: -lo 2) and FluxBasedFCT (-fct 1) run through the granular solver sequence on one block
+      const std::string who = fct == 1 ? "fct_type 1" : (cfg.lo_type == 2 ? "lo_type 2" : "lo_type 1");
+      if (many_blocks) { no = who + ": partitioned runs are not built for the DiscreteUpwind / FluxBasedFCT solvers (one block, rmhd_run with fused = 0)"; }
+      else if (cfg.fused) { no = who + ": the fused limiter and the one-kernel stage have their LO solver and clip + scale built in (fused must be 0)"; }
+      else if (cfg.ps) { no = who + ": product remap (ps) is not implemented for the DiscreteUpwind / FluxBasedFCT solvers"; }
+      else if (fct == 1 && cfg.pa) { no = "Flux-based FCT and PA are incompatible."; } // remhos.cpp:1088
+      else if (fct == 1 && cfg.self_wrap) { no = "fct_type 1: a self-wrapped block has ghost elements, which rmh_fct_fluxbased does not take"; }
+      if (!no.empty()) { return v; }
    }
-
-   if (cfg->mono_type && cd.dim == 3 && cd.order >= 4)
+   if (fct == 4)
    {
-      g_driver_error = "mono_type 1 (-mono 1): order " + std::to_string(cd.order) + " in 3-D is not supported: the element's mass matrix must stay in the LDS over the passes of the mass iteration (orders 1 to 3 in 3-D, 1 to 6 in 2-D)";
-      return -1;
+      if (partitioned_entry) { no = "rmhd_run_partitioned runs the one-kernel stage, which has clip + scale built in: fct_type 4 runs through rmhd_run / rmhd_run_rank with fused = 0"; }
+      else if (cfg.fused) { no = "fct_type 4: the fused limiter and the one-kernel stage have clip + scale built in (fused must be 0)"; }
+      else if (cfg.ps) { no = "fct_type 4: product remap (ps) is not implemented for the element FCT projection"; }
+      if (!no.empty()) { return v; }
    }
-
-   if (cfg->ps)
-   {
-      // what product remap (-ps) asks of the other options, in 3-D and in 2-D alike -- said before a device context exists
-      const char *why = nullptr;
-      if (cd.exec_mode != 1) { why = "Products are processed only in remap mode."; }                          // remhos.cpp:1713
-      else if (cfg->dt_control) { why = "Automatic time step is not implemented for product remap."; }        // remhos.cpp:1714
-      else if (cc.lo_type != 5) { why = "product remap is built for -lo 5 (what the fused limiter kernel takes)"; }
-      if (why) { g_driver_error = why; return -1; }
-   }
-
-   rmh_layout L;
-   L.dim = cd.dim; // (2: the reference's quadrilateral lattices, one rank -- build_case_2d)
-   L.order = cd.order;
-   L.mesh_order = 2;
-   L.exec_mode = cd.exec_mode;
-   L.ne_owned = cd.ne_owned;
-   L.ne_ghost = cd.ne_ghost; // (> 0 only for a self-wrapped block: rmhd_config.self_wrap)
-   L.x0 = cd.x0.data();
-   L.vel = cd.vel.data();
-   L.face_nbr = cd.face_nbr.data();
-   L.stencil27 = cd.stencil27.data();
-   L.subcell_vel = cd.subcell_vel.empty() ? nullptr : cd.subcell_vel.data();
-   L.device = device;
-   rmh_ctx *ctx = nullptr;
-   if (rmh_create(&L, &ctx) != 0) { g_driver_error = rmh_last_error(); return -1; }
-   if (cd.unstructured && rmh_set_quad_topology(ctx, cd.face_code.data(), cd.corner_ptr.data(), cd.corner_elems.data()) != 0)
-   {
-      g_driver_error = rmh_last_error();
-      rmh_destroy(ctx);
-      return -1;
-   }
-   rmh_enable_timers(ctx, 1);
-   bool reduce_over_ranks = false;
-   if (cd.ne_ghost > 0)
-   {
-      // The block has neighbours: the other blocks of the partition, one process each, over RCCL (comm_id_file) -- or,
-      // for a self-wrapped block, this rank itself.  The solver classes then run the exchanges the reference's would
-      // (SpaceLayout::ExchangeFaceNbrData / ExchangeElementExtrema) through the library's plan; a self-wrapped block
-      // without an id file uses a one-rank RCCL communicator, or device copies (RMH_EXCHANGE=local; always under the
-      // host emulation).
-      const int np = (int)cd.peers.size();
-      std::vector<int> prank(np), scount(np), rfirst(np), rcount(np);
-      std::vector<const int *> selems(np);
-      for (int j = 0; j < np; j++)
-      {
-         const Peer &pr = cd.peers[j];
-         prank[j] = pr.rank;
-         scount[j] = (int)pr.send_elems.size();
-         selems[j] = pr.send_elems.data();
-         rfirst[j] = pr.recv_slots.empty() ? 0 : pr.recv_slots.front();
-         rcount[j] = (int)pr.recv_slots.size();
-      }
-      rmh_exchange_desc d = {np, prank.data(), scount.data(), selems.data(), rfirst.data(), rcount.data()};
-      bool thin = false;
-      const int P3[3] = {cc.px, cc.py, cc.pz};
-      for (int dd = 0; dd < 3; dd++) { thin = thin || (P3[dd] > 1 && cd.n[dd] / P3[dd] < 2); }
-      const char *tr = std::getenv("RMH_EXCHANGE");
-      char id[128];
-      bool ok = rmh_exchange_setup(ctx, &d, thin ? 0 : 1) == 0;
-      if (ok && rccl_ranks)
-      {
-         if (cc.rank == 0) { std::remove(comm_id_file); ok = rmh_comm_unique_id(id) == 0; }
-         std::string why;
-         if (ok && !read_or_write_id(comm_id_file, cc.rank == 0, id)) { ok = false; why = "cannot exchange the RCCL unique id through the file"; }
-         if (!why.empty()) { g_driver_error = "neighbour exchange: " + why; rmh_destroy(ctx); return -1; }
-         ok = ok && rmh_comm_init(ctx, id, nranks, cc.rank) == 0;
-         if (ok && cc.rank == 0) { std::remove(comm_id_file); }
-         reduce_over_ranks = ok;
-      }
-      else if (ok && np == 1 && prank[0] == cc.rank && !(tr && std::string(tr) == "local") && rmh_comm_unique_id(id) == 0)
-      {
-         ok = rmh_comm_init(ctx, id, 1, 0) == 0;
-      }
-      else if (ok && np == 1 && prank[0] == cc.rank) { ok = rmh_comm_connect_local(ctx, 0, ctx, 0) == 0; }
-      else if (ok)
-      {
-         g_driver_error = "neighbour exchange: a block with neighbour ranks needs the RCCL id file";
-         rmh_destroy(ctx);
-         return -1;
-      }
-      if (!ok)
-      {
-         g_driver_error = std::string("neighbour exchange: ") + rmh_last_error();
-         rmh_destroy(ctx);
-         return -1;
-      }
-      if (cfg->fused && !cfg->ps && (cfg->ode_solver == 0 || cfg->ode_solver == 3))
-      {
-         g_driver_error = "a block with neighbours and the one-kernel stage runs through rmhd_run_partitioned";
-         rmh_destroy(ctx);
-         return -1;
-      }
-   }
-   if (rmh_set_bounds_type(ctx, cfg->bounds_type) != 0 || (cfg->dt_control && rmh_set_dt_control(ctx, 1) != 0))
-   {
-      g_driver_error = rmh_last_error();
-      rmh_destroy(ctx);
-      return -1;
-   }
-   const bool dtc = cfg->dt_control != 0;
-
-   const int vsize = cd.ne_owned * cd.ndof;
-   int rc = 0;
-   {
-      ParFiniteElementSpace pfes(ctx, cd.ne_owned, cd.ndof, (long long)cd.ne_global * cd.ndof, cd.ne_ghost > 0);
-      DofInfo dofs(pfes);
-      // solver factory of remhos.cpp:912-925, 927-995 for the options on the path
-      HOSolver *ho_solver = nullptr;
-      if (cfg->ho_type == 1) { ho_solver = new NeumannHOSolver(pfes); } // remhos.cpp:914-917
-      else if (cfg->ho_type == 2) { ho_solver = new CGHOSolver(pfes); }
-      else { ho_solver = new LocalInverseHOSolver(pfes, cfg->pa != 0); }
-      LOSolver *lo_solver = nullptr;
-      if (cc.lo_type == 5) { lo_solver = new MassBasedAvg(pfes, *ho_solver, nullptr); }
-      else if (cc.lo_type == 1) { lo_solver = new DiscreteUpwind(pfes, cd.exec_mode == 1); } // remhos.cpp:931-936
-      else if (cc.lo_type == 2) { lo_solver = new DiscreteUpwind(pfes, cd.exec_mode == 1, true); } // remhos.cpp:937-942
-      else if (cc.lo_type == 3) { lo_solver = new PAResidualDistribution(pfes); }
-      else { lo_solver = new PAResidualDistributionSubcell(pfes); }
-      double dt = cd.dt;
-      FCTSolver *fct_solver = nullptr; // remhos.cpp:983-995
-      if (cfg->fct_type == 4) { fct_solver = new ElementFCTProjection(pfes, dt); }
-      else if (cfg->fct_type == 1) { fct_solver = new FluxBasedFCT(pfes, nullptr, dt, 1); } // remhos.cpp:1086-1096
-      else { fct_solver = new ClipScaleSolver(pfes, nullptr, dt); }
-      // -ps / -s 11|12|13 (remhos.cpp:484-507, 875-904): block vector [u | us], IDP solvers.  They limit a COMBINATION of
-      // the stage's HO rate and the earlier limited updates, so the stage cannot be the one-kernel rmh_stage_fused:
-      // HO kernel + fused limiter kernel (fused = 1) or the reference's call sequence (fused = 0).
-      const bool ps = cfg->ps != 0;
-      const int ode_type = cfg->ode_solver ? cfg->ode_solver : 3;
-      const bool idp = ode_type > 10;
-      RMH_VERIFY(ode_type == 3 || ode_type == 11 || ode_type == 12 || ode_type == 13, "-s must be 3, 11, 12 or 13");
-      // fused = 1: one kernel per RK stage (rmh_stage_fused with the LO solver and the mass tolerance of the options)
-      const bool fused = cfg->fused != 0 && !ps && !idp;
-      if (fused)
-      {
-         RMH_CALL(rmh_set_lo_type(ctx, cc.lo_type));
-         if (cfg->ho_type == 2) { RMH_CALL(rmh_set_mass_tol(ctx, 1e-12, 0.0, 500)); }
-      }
-      AdvectionOperator adv(pfes, dofs, ho_solver, lo_solver, fct_solver, (ps || idp) && cfg->fused != 0 && cc.lo_type == 5, ps);
-      // Setup of the monolithic solver (if any): remhos.cpp:997-1006; mass_lim: :999
-      MonolithicSolver *mono_solver = nullptr;
-      if (cfg->mono_type == 1)
-      {
-         const std::vector<double> scale = mono_scale(cd, cc.problem);
-         const bool mass_lim = cc.problem != 6 && cc.problem != 7;
-         mono_solver = new MonoRDSolver(pfes, dofs, nullptr, scale.data(), false, cd.exec_mode == 1, mass_lim);
-         adv.mono_solver = mono_solver;
-      }
-      const bool vb = cfg->verify_bounds != 0;
-      adv.verify_bounds = vb;         // remhos.cpp:1115-1116
-      fct_solver->verify_bounds = vb;
-
-      // Primary scalar field is u; for product remap we also evolve us (remhos.cpp:875-904): S = [u | us]
-      Vector S((ps ? 2 : 1) * vsize);
-      Vector u(S.ReadWrite(), vsize);
-      u.CopyFromHost(cd.u0.data());
-      std::vector<double> h_u(vsize), h_m(vsize), h_us(ps ? vsize : 0);
-      if (ps)
-      {
-         // s = s0 where the element is active (BoolFunctionCoefficient on ComputeBoolIndicators(u), remhos.cpp:890-894),
-         // us = u * s node by node ("we don't target conservation at initialization", :899-900)
-         for (int e = 0; e < cd.ne_owned; e++)
-         {
-            bool active = false;
-            for (int i = 0; i < cd.ndof; i++) { active = active || cd.u0[(size_t)e * cd.ndof + i] > 1e-12; } // EMPTY_ZONE_TOL
-            for (int i = 0; i < cd.ndof; i++)
-            {
-               const size_t k = (size_t)e * cd.ndof + i;
-               h_us[k] = cd.u0[k] * (active ? cd.s0[k] : 0.0);
-            }
-         }
-         Vector us(S.ReadWrite() + vsize, vsize);
-         us.CopyFromHost(h_us.data());
-      }
-      // initial mass (remhos.cpp:1073-1076)
-      Vector masses(vsize);
-      RMH_CALL(rmh_compute_lumped_mass(ctx, 0.0, masses.Write()));
-      masses.CopyToHost(h_m.data());
-      // (sums of ~1e7 terms: accumulated in extended precision so that the printed mass carries no summation error of its
-      // own -- the conservation claims are at the 1e-12 level)
-      long double mass0_acc = 0.0L;
-      for (int i = 0; i < vsize; i++) { mass0_acc += (long double)h_m[i] * cd.u0[i]; }
-      // MPI_Allreduce of the report (remhos.cpp:1074-1081, 1412-1421) over the ranks of a partition: rmh_allreduce
-      auto reduce = [&](double v, int op) -> double
-      {
-         if (reduce_over_ranks) { RMH_CALL(rmh_allreduce(ctx, &v, 1, op)); }
-         return v;
-      };
-      const double mass0 = reduce((double)mass0_acc, 0);
-      long double mass0_us_acc = 0.0L;
-      for (int i = 0; i < (ps ? vsize : 0); i++) { mass0_us_acc += (long double)h_m[i] * h_us[i]; } // remhos.cpp:1077-1081
-
-      // Print the starting mesh and initial condition (remhos.cpp:1015-1030)
-      if (cfg->save)
-      {
-         const std::string e = save_mfem(cd, 0.0, cd.u0.data(), "meshHO_init.mesh", "sltn_init.gf");
-         RMH_VERIFY(e.empty(), e.c_str());
-      }
-      ODESolver *ode_solver_p = nullptr; // remhos.cpp:486-500
-      switch (ode_type)
-      {
-         case 11: ode_solver_p = new ForwardEulerIDPSolver(); break;
-         case 12: ode_solver_p = new RK2IDPSolver(); break;
-         case 13: ode_solver_p = new RK3IDPSolver(); break;
-         default: ode_solver_p = new RK3SSPSolver(); break;
-      }
-      ODESolver &ode_solver = *ode_solver_p;
-      const int stages_per_step = ode_type == 11 ? 1 : (ode_type == 12 ? 2 : 3);
-      double t = 0.0;
-      adv.SetTime(t);
-      ode_solver.Init(adv);
-      // For remap, the pseudo-time always evolves from 0 to 1 (remhos.cpp:1128-1134)
-      const double t_final = cd.exec_mode == 1 ? 1.0 : cc.t_final;
-      bool done = false;
-      int ti = 0, ti_total = 0; // accepted steps / all steps incl. repeated ones (remhos.cpp:1142)
-      HIP_CALL(hipDeviceSynchronize());
-      const auto w0 = std::chrono::steady_clock::now();
-      Vector y1(fused ? vsize : 0), y2(fused ? vsize : 0);
-      unsigned long long tok_u = 0;
-      Vector Sold(dtc ? vsize : 0);
-      int repeats = 0;
-      // -vb: global extrema of u (GetMinMax, remhos.cpp:1124) and of s = us / u on its active dofs (ComputeMinMaxS,
-      // remhos_sync.cpp:116-140) -- element extrema on the device, the ne values reduced on the host (a debug mode)
-      Vector vb_du(vb && fused ? vsize : 0), vb_s(vb && ps ? vsize : 0);
-      bool *vb_flags = nullptr;
-      if (vb && ps) { HIP_CALL(hipMalloc((void **)&vb_flags, (size_t)cd.ne_owned + vsize)); }
-      std::vector<double> h_emin(vb ? cd.ne_owned : 0), h_emax(vb ? cd.ne_owned : 0);
-      auto global_minmax = [&](const Vector &v, Array<bool> *el, Array<bool> *df, double &lo, double &hi)
-      {
-         dofs.ComputeElementsMinMax(v, dofs.xe_min, dofs.xe_max, el, df);
-         dofs.xe_min.CopyToHost(h_emin.data());
-         dofs.xe_max.CopyToHost(h_emax.data());
-         lo = INFINITY;
-         hi = -INFINITY;
-         for (int e = 0; e < cd.ne_owned; e++) { lo = std::fmin(lo, h_emin[e]); hi = std::fmax(hi, h_emax[e]); }
-         lo = reduce(lo, 1);
-         hi = reduce(hi, 2);
-      };
-      auto s_minmax = [&](double &lo, double &hi)
-      {
-         Vector us(S.ReadWrite() + vsize, vsize);
-         Array<bool> el(vb_flags, cd.ne_owned), df(vb_flags + cd.ne_owned, vsize);
-         ComputeRatio(pfes, us, u, vb_s, el, df);
-         global_minmax(vb_s, &el, &df, lo, hi);
-      };
-      double u_min_glob = 0., u_max_glob = 0., s_min_glob = 0., s_max_glob = 0.;
-      if (vb)
-      {
-         global_minmax(u, nullptr, nullptr, u_min_glob, u_max_glob);
-         if (ps) { s_minmax(s_min_glob, s_max_glob); }
-      }
-      while (!done)
-      {
-         // Monotonicity check for debug purposes mainly (remhos.cpp:1218-1262; forced_bounds holds for every LO solver here)
-         if (vb)
-         {
-            const double eps = 1e-10;
-            double u_min_new, u_max_new, s_min_new = s_min_glob, s_max_new = s_max_glob;
-            global_minmax(u, nullptr, nullptr, u_min_new, u_max_new);
-            if (ps) { s_minmax(s_min_new, s_max_new); }
-            const bool unit_range = cc.problem % 10 == 6 || cc.problem % 10 == 7;
-            const double ulo = unit_range ? 0.0 : u_min_glob, uhi = unit_range ? 1.0 : u_max_glob;
-            const double slo = unit_range ? 0.0 : s_min_glob, shi = unit_range ? 1.0 : s_max_glob;
-            char msg[96];
-            std::snprintf(msg, sizeof(msg), "Undershoot of %.6e", ulo - u_min_new);
-            RMH_VERIFY(u_min_new > ulo - eps, msg);
-            std::snprintf(msg, sizeof(msg), "Overshoot of %.6e", u_max_new - uhi);
-            RMH_VERIFY(u_max_new < uhi + eps, msg);
-            std::snprintf(msg, sizeof(msg), "Undershoot in s of %.6e", slo - s_min_new);
-            RMH_VERIFY(s_min_new > slo - eps, msg);
-            std::snprintf(msg, sizeof(msg), "Overshoot in s of %.6e", s_max_new - shi);
-            RMH_VERIFY(s_max_new < shi + eps, msg);
-            if (!unit_range) { u_min_glob = u_min_new; u_max_glob = u_max_new; } // (s_min / s_max stay the initial ones, like the reference's)
-         }
-         double dt_real = std::min(dt, t_final - t);
-         // This also resets the time step estimate when automatic dt is on (remhos.cpp:1150-1152)
-         adv.SetDt(dt_real);
-         if (dtc)
-         {
-            adv.ResetTimeStepRatio();
-            Sold = u;
-         }
-         if (fused && vb)
-         {
-            // the one-kernel stage under -vb: the kernel also hands out the limited rate, and the granular kernels form the
-            // dof bounds of the stage input for the check of remhos.cpp:1833-1837 (the LO rate never leaves the kernel:
-            // its check, :1824-1828, is the granular sequence's -- rmhd_config.fused = 0)
-            const int ne = cd.ne_owned;
-            auto stage = [&](const Vector &in, double ts, const double *xb, double a, double b, Vector &out)
-            {
-               RMH_CALL(rmh_setup(ctx, ts));
-               RMH_CALL(rmh_stage_fused_chain(ctx, in.Read(), dt_real, xb, a, b, dt_real, out.Write(), vb_du.Write(), 0, ne, 1, 0, nullptr));
-               dofs.ComputeElementsMinMax(in, dofs.xe_min, dofs.xe_max);
-               dofs.ComputeBounds(dofs.xe_min, dofs.xe_max, dofs.xi_min, dofs.xi_max);
-               check_violation(pfes, in, dt_real, vb_du, dofs.xi_min, dofs.xi_max, "LimitMult FCT solution u", 1e-12, nullptr);
-            };
-            stage(u, t, nullptr, 0.0, 1.0, y1);
-            stage(y1, t + dt_real, u.Read(), 3. / 4, 1. / 4, y2);
-            stage(y2, t + dt_real / 2, u.Read(), 1. / 3, 2. / 3, u); // (y_out may alias x_base)
-            tok_u = 0;
-            t += dt_real;
-         }
-         else if (fused)
-         {
-            // one kernel per RK stage (rmh_stage_fused): same stage times and combinations as
-            // RK3SSPSolver::Step; input and output vectors of a stage differ
-            // (tok_u names the element extrema of u left by the stage that wrote it: rmh_stage_fused_chain)
-            unsigned long long tok = 0;
-            const int ne = cd.ne_owned;
-            RMH_CALL(rmh_setup(ctx, t));
-            RMH_CALL(rmh_stage_fused_chain(ctx, u.Read(), dt_real, nullptr, 0.0, 1.0, dt_real, y1.Write(), nullptr, 0, ne, 1, tok_u, &tok));
-            RMH_CALL(rmh_setup(ctx, t + dt_real));
-            RMH_CALL(rmh_stage_fused_chain(ctx, y1.Read(), dt_real, u.Read(), 3. / 4, 1. / 4, dt_real, y2.Write(), nullptr, 0, ne, 1, tok, &tok));
-            RMH_CALL(rmh_setup(ctx, t + dt_real / 2));
-            RMH_CALL(rmh_stage_fused_chain(ctx, y2.Read(), dt_real, u.Read(), 1. / 3, 2. / 3, dt_real, u.Write(), nullptr, 0, ne, 1, tok, &tok_u));
-            t += dt_real;
-         }
-         else { ode_solver.Step(S, t, dt_real); }
-         ti++;
-         ti_total++;
-         if (dtc)
-         {
-            // remhos.cpp:1178-1197; the estimate is the minimum over the ranks of a partition (MPI_Allreduce(MIN),
-            // remhos.cpp:1993): every rank takes the same accept / repeat decision, hence issues the same exchanges
-            const double dt_ratio = reduce(adv.GetTimeStepRatio(), 1);
-            if (dt_ratio < 1.)
-            {
-               // Repeat with the proper time step.
-               ti--;
-               t -= dt_real;
-               u = Sold;
-               tok_u = 0; // (u is no longer the output of the last stage)
-               dt = 0.85 * dt;
-               repeats++;
-               RMH_VERIFY(dt >= 1e-12, "The time step crashed!");
-               continue;
-            }
-            else if (dt_ratio > 1.25) { dt *= 1.02; }
-         }
-         done = (t >= t_final - 1.e-8 * dt);
-         if (ti_total == cc.max_steps) { done = true; } // -ms counts repeated steps too (remhos.cpp:1296)
-      }
-      HIP_CALL(hipDeviceSynchronize());
-      const auto w1 = std::chrono::steady_clock::now();
-      if (vb_flags) { (void)hipFree(vb_flags); }
-
-      // final mass: remap uses the lumped mass at the final position (remhos.cpp:1382-1413)
-      if (cd.exec_mode == 1)
-      {
-         RMH_CALL(rmh_compute_lumped_mass(ctx, t, masses.Write()));
-         masses.CopyToHost(h_m.data());
-      }
-      u.CopyToHost(h_u.data());
-      // Print the final mesh and solution (remhos.cpp:1365-1380)
-      if (cfg->save)
-      {
-         const std::string e = save_mfem(cd, t, h_u.data(), "meshHO_final.mesh", "sltn_final.gf");
-         RMH_VERIFY(e.empty(), e.c_str());
-      }
-      long double mass_acc = 0.0L;
-      double umax = -INFINITY;
-      for (int i = 0; i < vsize; i++)
-      {
-         mass_acc += (long double)h_m[i] * h_u[i];
-         umax = std::fmax(umax, h_u[i]);
-      }
-      const double mass = reduce((double)mass_acc, 0);
-      umax = reduce(umax, 2);
-      if (u_final) { std::copy(h_u.begin(), h_u.end(), u_final); }
-      {
-         // Compute errors, if the exact solution is known (remhos.cpp:1438-1470)
-         double es[3];
-         if (lp_error_sums(cd, cc.problem, t, h_u.data(), es).empty())
-         {
-            res->has_errors = 1;
-            res->err_l1 = reduce(es[0], 0);
-            res->err_l2 = std::sqrt(reduce(es[1], 0));
-            res->err_linf = reduce(es[2], 2);
-         }
-      }
-      if (ps)
-      {
-         // remhos.cpp:1404, 1416-1434: mass of us with the same lumped masses; max of the ratio s = us / u
-         Vector us(S.ReadWrite() + vsize, vsize), s_fin(vsize);
-         us.CopyToHost(h_us.data());
-         if (us_final) { std::copy(h_us.begin(), h_us.end(), us_final); }
-         long double acc = 0.0L;
-         for (int i = 0; i < vsize; i++) { acc += (long double)h_m[i] * h_us[i]; }
-         bool *flags = nullptr;
-         HIP_CALL(hipMalloc((void **)&flags, (size_t)cd.ne_owned + vsize));
-         Array<bool> el(flags, cd.ne_owned), dfl(flags + cd.ne_owned, vsize);
-         ComputeRatio(pfes, us, u, s_fin, el, dfl);
-         std::vector<double> h_s(vsize);
-         s_fin.CopyToHost(h_s.data());
-         (void)hipFree(flags);
-         double smax = -INFINITY;
-         for (int i = 0; i < vsize; i++) { smax = std::fmax(smax, h_s[i]); }
-         res->final_mass_us = reduce((double)acc, 0);
-         res->mass0_us = reduce((double)mass0_us_acc, 0);
-         res->mass_loss_us = std::fabs(res->mass0_us - res->final_mass_us);
-         res->s_max = reduce(smax, 2);
-      }
-      adv.Timer().Update(ctx);
-      const TimingData &T = adv.Timer();
-      res->final_mass = mass;
-      res->max_value = umax;
-      res->mass0 = mass0;
-      res->mass_loss = std::fabs(mass0 - mass);
-      res->dt = dt;
-      res->t_end = t;
-      res->steps = ti;
-      res->stages = stages_per_step * ti_total; // the FOMs count repeated steps too (remhos.cpp:1340-1348)
-      res->global_dofs = pfes.GlobalVSize();
-      res->t_rhs = T.sw_rhs;
-      res->t_inv = T.sw_L2inv;
-      res->t_lo = T.sw_LO;
-      res->t_fct = T.sw_FCT;
-      res->t_total = T.sw_rhs + T.sw_LO + T.sw_FCT; // remhos.cpp:1933 (omits INV)
-      const double dofs_steps = 1e-6 * (double)res->global_dofs * res->stages;
-      res->fom_rhs = T.sw_rhs > 0 ? dofs_steps / T.sw_rhs : 0;
-      res->fom_inv = T.sw_L2inv > 0 ? dofs_steps / T.sw_L2inv : 0;
-      res->fom_lo = T.sw_LO > 0 ? dofs_steps / T.sw_LO : 0;
-      res->fom_fct = T.sw_FCT > 0 ? dofs_steps / T.sw_FCT : 0;
-      res->fom = res->t_total > 0 ? dofs_steps / res->t_total : 0;
-      res->wall = std::chrono::duration<double>(w1 - w0).count();
-      res->fom_wall = dofs_steps / res->wall;
-      int it = 0;
-      rmh_last_cg_iters(ctx, &it);
-      res->cg_iters_max = it;
-      res->repeats = repeats;
-      delete ode_solver_p;
-      delete mono_solver;
-      delete fct_solver;
-      delete lo_solver;
-      delete ho_solver;
-   }
-   rmh_destroy(ctx);
-   return rc;
+   // the entry point's own rule
+   const CaseConfig cc = to_config(cfg);
+   if (partitioned_entry && !cfg.fused) { no = "rmhd_run_partitioned runs the one-kernel stage (fused = 1)"; }
+   else if (!partitioned_entry && cc.px * cc.py * cc.pz != 1 && !id_file) { no = "rmhd_run drives one block; box-partitioned runs go through rmhd_run_partitioned, or through rmhd_run_rank with one process per block"; }
+   return v;
 }
 
+// The refusals that need the built case: its dimension, order and exec_mode
+std::string check_case(const rmhd_config &cfg, const CaseConfig &cc, const CaseData &cd, bool partitioned_entry)
+{
+   if (partitioned_entry) { return cd.dim != 3 ? "the partitioned stage loop is for the 3-D cases" : ""; }
+   if (cc.lo_type == 2 && cd.dim == 3 && cd.order >= 4) { return "lo_type 2 (-lo 2): order " + std::to_string(cd.order) + " in 3-D is not supported: the element's dense matrices must fit the LDS (orders 1 to 3 in 3-D, 1 to 6 in 2-D)"; }
+   if (cfg.mono_type && cd.dim == 3 && cd.order >= 4) { return "mono_type 1 (-mono 1): order " + std::to_string(cd.order) + " in 3-D is not supported: the element's mass matrix must stay in the LDS over the passes of the mass iteration (orders 1 to 3 in 3-D, 1 to 6 in 2-D)"; }
+   if (cfg.ps)
+   {
+      // what product remap (-ps) asks of the other options, in 3-D and in 2-D alike
+      if (cd.exec_mode != 1) { return "Products are processed only in remap mode."; }                  // remhos.cpp:1713
+      if (cfg.dt_control) { return "Automatic time step is not implemented for product remap."; }      // remhos.cpp:1714
+      if (cc.lo_type != 5) { return "product remap is built for -lo 5 (what the fused limiter kernel takes)"; }
+   }
+   return "";
+}
 
-// ---- box-partitioned runs: the time loop of remhos() (remhos.cpp:1146-1330) over the blocks of a ParMesh-like
-// partition, one fused kernel per RK stage and block, one neighbour exchange per stage (rmh_exchange_begin / _end) ----
-namespace
+// ---- set-up pieces of both time loops ------------------------------------------------------------------------------------
+struct CtxDelete { void operator()(rmh_ctx *c) const { rmh_destroy(c); } };
+typedef std::unique_ptr<rmh_ctx, CtxDelete> CtxPtr;
+
+rmh_layout make_layout(const CaseData &cd, int device)
 {
-struct Block
+   rmh_layout L;
+   L.dim = cd.dim; L.order = cd.order; L.mesh_order = 2; L.exec_mode = cd.exec_mode; // (dim 2: build_case_2d, one rank)
+   L.ne_owned = cd.ne_owned; L.ne_ghost = cd.ne_ghost; // (> 0: a self-wrapped block -- rmhd_config.self_wrap -- or a block of a partition)
+   L.x0 = cd.x0.data(); L.vel = cd.vel.data(); L.face_nbr = cd.face_nbr.data(); L.stencil27 = cd.stencil27.data();
+   L.subcell_vel = cd.subcell_vel.empty() ? nullptr : cd.subcell_vel.data();
+   L.device = device;
+   return L;
+}
+
+// The exchange plan of a block from the case builder's halo lists; compact records unless a block is one element thin
+struct ExchangePlan
 {
-   CaseData cd;
-   rmh_ctx *ctx = nullptr;
-   double *x = nullptr, *y1 = nullptr, *y2 = nullptr, *xold = nullptr, *m = nullptr;
-   int vsize = 0;
-   unsigned long long tok = 0; // token of the extrema of the vector the next stage reads (rmh_stage_fused_chain)
-   hipStream_t stream = nullptr; // the context's stream: a non-blocking one, so that the exchange stream overlaps it
+   std::vector<int> prank, scount, rfirst, rcount;
+   std::vector<const int *> selems;
+   bool thin = false;
+   ExchangePlan(const CaseData &cd, const CaseConfig &cc)
+   {
+      for (const Peer &pr : cd.peers)
+      {
+         prank.push_back(pr.rank);
+         scount.push_back((int)pr.send_elems.size());
+         selems.push_back(pr.send_elems.data());
+         rfirst.push_back(pr.recv_slots.empty() ? 0 : pr.recv_slots.front());
+         rcount.push_back((int)pr.recv_slots.size());
+      }
+      const int P3[3] = {cc.px, cc.py, cc.pz};
+      for (int dd = 0; dd < 3; dd++) { thin = thin || (P3[dd] > 1 && cd.n[dd] / P3[dd] < 2); }
+   }
+   bool only_peer_is(int rank) const { return prank.size() == 1 && prank[0] == rank; }
+   int setup(rmh_ctx *ctx) const
+   {
+      const rmh_exchange_desc d = {(int)prank.size(), prank.data(), scount.data(), selems.data(), rfirst.data(), rcount.data()};
+      return rmh_exchange_setup(ctx, &d, thin ? 0 : 1);
+   }
 };
 
 // ncclUniqueId rendezvous through a file.  Record = magic, launch tag, id.  The launch tag is what tells this launch's
@@ -1233,12 +808,7 @@ struct Block
 // and renames it; the others poll until they read a record with their tag that is fresh: not older than five minutes with a
 // nonce, not older than the reader's own start (less 30 s) without.  Rank 0 deletes the file once ncclCommInitRank -- a
 // collective -- has returned.
-struct IdRecord
-{
-   char magic[8];
-   long long tag;
-   char id[128];
-};
+struct IdRecord { char magic[8]; long long tag; char id[128]; };
 
 long long launch_tag()
 {
@@ -1283,7 +853,474 @@ bool read_or_write_id(const char *path, bool writer, char id[128])
    }
    return false;
 }
+
+// The RCCL communicator of `nranks` processes for ctx: rank 0 removes a stale file, makes the id and writes it, every rank reads it
+// and joins; rank 0 removes the file once every rank has read it (ncclCommInitRank is collective).  nullptr on success; else what
+// failed: ID_FILE_FAILED, or the name of the rmh_* call whose reason rmh_last_error() has.
+const char *const ID_FILE_FAILED = "cannot exchange the RCCL unique id through the file";
+const char *rccl_rendezvous(rmh_ctx *ctx, const char *comm_id_file, int nranks, int rank)
+{
+   char id[128];
+   if (rank == 0)
+   {
+      std::remove(comm_id_file); // (a stale record: see read_or_write_id)
+      if (rmh_comm_unique_id(id) != 0) { return "rmh_comm_unique_id"; }
+   }
+   if (!read_or_write_id(comm_id_file, rank == 0, id)) { return ID_FILE_FAILED; }
+   if (rmh_comm_init(ctx, id, nranks, rank) != 0) { return "rmh_comm_init"; }
+   if (rank == 0) { std::remove(comm_id_file); }
+   return nullptr;
+}
+
+// MPI_Allreduce of the reports and of the -dtc estimate (remhos.cpp:1074-1081, 1412-1421, 1993) over the ranks of a communicator:
+// rmh_allreduce (op 0 sum, 1 min, 2 max).  ctx = null: one process, nothing to reduce.  A failure aborts (strict) or is remembered.
+struct Reduce
+{
+   rmh_ctx *ctx;
+   bool strict;
+   bool failed = false;
+   double operator()(double v, int op)
+   {
+      if (ctx && rmh_allreduce(ctx, &v, 1, op) != 0) { RMH_VERIFY(!strict, "rmh_allreduce(ctx, &v, 1, op)"); failed = true; }
+      return v;
+   }
+};
+
+// The step bookkeeping of remhos.cpp:1142-1197, 1296 for both time loops
+struct StepClock
+{
+   double t = 0.0, dt = 0.0, t_final = 0.0;
+   int max_steps = -1, repeats = 0;
+   int ti = 0, ti_total = 0; // accepted steps / all steps incl. repeated ones (remhos.cpp:1142)
+
+   double next_dt() const { return std::min(dt, t_final - t); }
+   void count_step() { ti++; ti_total++; }
+   // -dtc (remhos.cpp:1178-1197): false = the step of dt_real is taken back and repeated with 0.85 dt -- the caller restores its
+   // state and looks at crashed() -- else dt may grow
+   bool accept(double dt_ratio, double dt_real)
+   {
+      if (dt_ratio < 1.) { ti--; t -= dt_real; dt = 0.85 * dt; repeats++; return false; }
+      if (dt_ratio > 1.25) { dt *= 1.02; }
+      return true;
+   }
+   bool crashed() const { return !(dt >= 1e-12); } // "The time step crashed!"
+   // -ms counts repeated steps too (remhos.cpp:1296)
+   bool done() const { return t >= t_final - 1.e-8 * dt || ti_total == max_steps; }
+};
+
+// What both entry points report alike: masses, dt, step counts, the stopwatches T = (rhs, inv, lo, fct) with their figures of merit
+// over `fom_stages` stages, wall clock, CG iterations, repeats
+void fill_result_tail(rmhd_result *res, double mass0, double mass, double umax, const StepClock &clock, int stages_per_step,
+                      long long global_dofs, int fom_stages, const double T[4], double wall, int cg_iters)
+{
+   res->final_mass = mass; res->max_value = umax; res->mass0 = mass0; res->mass_loss = std::fabs(mass0 - mass);
+   res->dt = clock.dt; res->t_end = clock.t; res->steps = clock.ti;
+   res->stages = stages_per_step * clock.ti_total; // the FOMs count repeated steps too (remhos.cpp:1340-1348)
+   res->global_dofs = global_dofs;
+   res->t_rhs = T[0]; res->t_inv = T[1]; res->t_lo = T[2]; res->t_fct = T[3];
+   res->t_total = T[0] + T[2] + T[3]; // remhos.cpp:1933 (omits INV)
+   const double dofs_steps = 1e-6 * (double)global_dofs * fom_stages;
+   res->fom_rhs = T[0] > 0 ? dofs_steps / T[0] : 0;
+   res->fom_inv = T[1] > 0 ? dofs_steps / T[1] : 0;
+   res->fom_lo = T[2] > 0 ? dofs_steps / T[2] : 0;
+   res->fom_fct = T[3] > 0 ? dofs_steps / T[3] : 0;
+   res->fom = res->t_total > 0 ? dofs_steps / res->t_total : 0;
+   res->wall = wall; res->fom_wall = dofs_steps / wall;
+   res->cg_iters_max = cg_iters; res->repeats = clock.repeats;
+}
+
+// ---- one block through the solver classes: rmhd_run, rmhd_run_state, rmhd_run_rank -------------------------------------------
+// A block with neighbours (ne_ghost > 0) has the other blocks of the partition, one process each, over RCCL (comm_id_file) -- or,
+// self-wrapped, this rank itself.  The solver classes then run the exchanges the reference's would (SpaceLayout::
+// ExchangeFaceNbrData / ExchangeElementExtrema) through the library's plan; a self-wrapped block without an id file uses a one-rank
+// RCCL communicator, or device copies (RMH_EXCHANGE=local; always under the host emulation).  Returns the refusal, or ""
+std::string connect_neighbours(rmh_ctx *ctx, const CaseConfig &cc, const CaseData &cd, const char *comm_id_file, bool &reduce_over_ranks)
+{
+   const std::string head = "neighbour exchange: ";
+   const ExchangePlan plan(cd, cc);
+   const char *tr = std::getenv("RMH_EXCHANGE");
+   char id[128];
+   bool ok = plan.setup(ctx) == 0;
+   if (ok && comm_id_file)
+   {
+      const char *failed = rccl_rendezvous(ctx, comm_id_file, cc.px * cc.py * cc.pz, cc.rank);
+      if (failed == ID_FILE_FAILED) { return head + ID_FILE_FAILED; }
+      reduce_over_ranks = ok = !failed;
+   }
+   else if (ok && plan.only_peer_is(cc.rank) && !(tr && std::string(tr) == "local") && rmh_comm_unique_id(id) == 0) { ok = rmh_comm_init(ctx, id, 1, 0) == 0; }
+   else if (ok && plan.only_peer_is(cc.rank)) { ok = rmh_comm_connect_local(ctx, 0, ctx, 0) == 0; }
+   else if (ok) { return head + "a block with neighbour ranks needs the RCCL id file"; }
+   return ok ? "" : head + rmh_last_error();
+}
+
+// The context of the block: rmh_create, the tables of a mesh file, the neighbour exchange, -bt, -dtc.  Returns the refusal, or ""
+// (a context that a refusal leaves in `ctx` is the caller's to destroy: CtxPtr does)
+std::string open_context(const rmhd_config &cfg, const CaseConfig &cc, const CaseData &cd, const char *comm_id_file, int device,
+                         CtxPtr &ctx, bool &reduce_over_ranks)
+{
+   const rmh_layout L = make_layout(cd, device);
+   rmh_ctx *c = nullptr;
+   if (rmh_create(&L, &c) != 0) { return rmh_last_error(); }
+   ctx.reset(c);
+   if (cd.unstructured && rmh_set_quad_topology(c, cd.face_code.data(), cd.corner_ptr.data(), cd.corner_elems.data()) != 0) { return rmh_last_error(); }
+   rmh_enable_timers(c, 1);
+   if (cd.ne_ghost > 0)
+   {
+      const std::string why = connect_neighbours(c, cc, cd, comm_id_file, reduce_over_ranks);
+      if (!why.empty()) { return why; }
+      if (cfg.fused && !cfg.ps && (cfg.ode_solver == 0 || cfg.ode_solver == 3)) { return "a block with neighbours and the one-kernel stage runs through rmhd_run_partitioned"; }
+   }
+   if (rmh_set_bounds_type(c, cfg.bounds_type) != 0 || (cfg.dt_control && rmh_set_dt_control(c, 1) != 0)) { return rmh_last_error(); }
+   return "";
+}
+
+struct Solvers
+{
+   std::unique_ptr<HOSolver> ho; std::unique_ptr<LOSolver> lo; std::unique_ptr<FCTSolver> fct; std::unique_ptr<ODESolver> ode;
+   int ode_type = 3, stages_per_step = 3;
+   bool fused = false; // one kernel per RK stage (rmh_stage_fused with the LO solver and the mass tolerance of the options)
+};
+
+// solver factory of remhos.cpp:912-925, 927-995, 486-500 for the options on the path
+Solvers make_solvers(const rmhd_config &cfg, const CaseConfig &cc, const CaseData &cd, ParFiniteElementSpace &pfes)
+{
+   Solvers s;
+   if (cfg.ho_type == 1) { s.ho.reset(new NeumannHOSolver(pfes)); } // remhos.cpp:914-917
+   else if (cfg.ho_type == 2) { s.ho.reset(new CGHOSolver(pfes)); }
+   else { s.ho.reset(new LocalInverseHOSolver(pfes, cfg.pa != 0)); }
+   if (cc.lo_type == 5) { s.lo.reset(new MassBasedAvg(pfes, *s.ho, nullptr)); }
+   else if (cc.lo_type == 1) { s.lo.reset(new DiscreteUpwind(pfes, cd.exec_mode == 1)); } // remhos.cpp:931-936
+   else if (cc.lo_type == 2) { s.lo.reset(new DiscreteUpwind(pfes, cd.exec_mode == 1, true)); } // remhos.cpp:937-942
+   else if (cc.lo_type == 3) { s.lo.reset(new PAResidualDistribution(pfes)); }
+   else { s.lo.reset(new PAResidualDistributionSubcell(pfes)); }
+   // remhos.cpp:983-995
+   if (cfg.fct_type == 4) { s.fct.reset(new ElementFCTProjection(pfes, cd.dt)); }
+   else if (cfg.fct_type == 1) { s.fct.reset(new FluxBasedFCT(pfes, nullptr, cd.dt, 1)); } // remhos.cpp:1086-1096
+   else { s.fct.reset(new ClipScaleSolver(pfes, nullptr, cd.dt)); }
+   // -ps / -s 11|12|13 (remhos.cpp:484-507, 875-904): block vector [u | us], IDP solvers.  They limit a COMBINATION of
+   // the stage's HO rate and the earlier limited updates, so the stage cannot be the one-kernel rmh_stage_fused:
+   // HO kernel + fused limiter kernel (fused = 1) or the reference's call sequence (fused = 0).
+   s.ode_type = cfg.ode_solver ? cfg.ode_solver : 3;
+   RMH_VERIFY(s.ode_type == 3 || s.ode_type == 11 || s.ode_type == 12 || s.ode_type == 13, "-s must be 3, 11, 12 or 13");
+   s.fused = cfg.fused != 0 && !cfg.ps && s.ode_type == 3;
+   if (s.fused)
+   {
+      RMH_CALL(rmh_set_lo_type(pfes.Ctx(), cc.lo_type));
+      if (cfg.ho_type == 2) { RMH_CALL(rmh_set_mass_tol(pfes.Ctx(), 1e-12, 0.0, 500)); }
+   }
+   switch (s.ode_type) // remhos.cpp:486-500
+   {
+      case 11: s.ode.reset(new ForwardEulerIDPSolver()); break;
+      case 12: s.ode.reset(new RK2IDPSolver()); break;
+      case 13: s.ode.reset(new RK3IDPSolver()); break;
+      default: s.ode.reset(new RK3SSPSolver()); break;
+   }
+   s.stages_per_step = s.ode_type == 11 ? 1 : (s.ode_type == 12 ? 2 : 3);
+   return s;
+}
+
+// Setup of the monolithic solver (if any): remhos.cpp:997-1006; mass_lim: :999
+std::unique_ptr<MonolithicSolver> make_mono_solver(const rmhd_config &cfg, const CaseConfig &cc, const CaseData &cd,
+                                                   ParFiniteElementSpace &pfes, DofInfo &dofs)
+{
+   if (cfg.mono_type != 1) { return nullptr; }
+   const std::vector<double> scale = mono_scale(cd, cc.problem);
+   const bool mass_lim = cc.problem != 6 && cc.problem != 7;
+   return std::unique_ptr<MonolithicSolver>(new MonoRDSolver(pfes, dofs, nullptr, scale.data(), false, cd.exec_mode == 1, mass_lim));
+}
+
+// -vb: global extrema of u (GetMinMax, remhos.cpp:1124) and of s = us / u on its active dofs (ComputeMinMaxS,
+// remhos_sync.cpp:116-140) -- element extrema on the device, the ne values reduced on the host (a debug mode) -- and the
+// monotonicity check of every step against them
+struct VbMonitor
+{
+   ParFiniteElementSpace &pfes; DofInfo &dofs; Reduce &reduce;
+   const int ne, vsize;
+   const bool ps, unit_range;
+   Vector vb_s;
+   bool *vb_flags = nullptr;
+   std::vector<double> h_emin, h_emax;
+   double u_min_glob = 0., u_max_glob = 0., s_min_glob = 0., s_max_glob = 0.;
+
+   VbMonitor(ParFiniteElementSpace &pfes_, DofInfo &dofs_, Reduce &reduce_, bool ps_, int problem)
+      : pfes(pfes_), dofs(dofs_), reduce(reduce_), ne(pfes_.GetNE()), vsize(pfes_.GetVSize()), ps(ps_),
+        unit_range(problem % 10 == 6 || problem % 10 == 7), vb_s(ps_ ? pfes_.GetVSize() : 0), h_emin(ne), h_emax(ne)
+   {
+      if (ps) { HIP_CALL(hipMalloc((void **)&vb_flags, (size_t)ne + vsize)); }
+   }
+   ~VbMonitor() { if (vb_flags) { (void)hipFree(vb_flags); } }
+   VbMonitor(const VbMonitor &) = delete; // (and with it the assignment: the reference members)
+
+   void global_minmax(const Vector &v, Array<bool> *el, Array<bool> *df, double &lo, double &hi)
+   {
+      dofs.ComputeElementsMinMax(v, dofs.xe_min, dofs.xe_max, el, df);
+      dofs.xe_min.CopyToHost(h_emin.data());
+      dofs.xe_max.CopyToHost(h_emax.data());
+      lo = INFINITY; hi = -INFINITY;
+      for (int e = 0; e < ne; e++) { lo = std::fmin(lo, h_emin[e]); hi = std::fmax(hi, h_emax[e]); }
+      lo = reduce(lo, 1);
+      hi = reduce(hi, 2);
+   }
+   // the extrema of u and, with -ps, of s for S = [u | us]
+   void minmax_of(Vector &S, double &ulo, double &uhi, double &slo, double &shi)
+   {
+      const Vector u(S.ReadWrite(), vsize);
+      global_minmax(u, nullptr, nullptr, ulo, uhi);
+      if (!ps) { return; }
+      const Vector us(S.ReadWrite() + vsize, vsize);
+      Array<bool> el(vb_flags, ne), df(vb_flags + ne, vsize);
+      ComputeRatio(pfes, us, u, vb_s, el, df);
+      global_minmax(vb_s, &el, &df, slo, shi);
+   }
+   void start(Vector &S) { minmax_of(S, u_min_glob, u_max_glob, s_min_glob, s_max_glob); }
+   // Monotonicity check for debug purposes mainly (remhos.cpp:1218-1262; forced_bounds holds for every LO solver here)
+   void check(Vector &S)
+   {
+      const double eps = 1e-10;
+      double u_min_new, u_max_new, s_min_new = s_min_glob, s_max_new = s_max_glob;
+      minmax_of(S, u_min_new, u_max_new, s_min_new, s_max_new);
+      const double ulo = unit_range ? 0.0 : u_min_glob, uhi = unit_range ? 1.0 : u_max_glob;
+      const double slo = unit_range ? 0.0 : s_min_glob, shi = unit_range ? 1.0 : s_max_glob;
+      char msg[96];
+      std::snprintf(msg, sizeof(msg), "Undershoot of %.6e", ulo - u_min_new); RMH_VERIFY(u_min_new > ulo - eps, msg);
+      std::snprintf(msg, sizeof(msg), "Overshoot of %.6e", u_max_new - uhi); RMH_VERIFY(u_max_new < uhi + eps, msg);
+      std::snprintf(msg, sizeof(msg), "Undershoot in s of %.6e", slo - s_min_new); RMH_VERIFY(s_min_new > slo - eps, msg);
+      std::snprintf(msg, sizeof(msg), "Overshoot in s of %.6e", s_max_new - shi); RMH_VERIFY(s_max_new < shi + eps, msg);
+      if (!unit_range) { u_min_glob = u_min_new; u_max_glob = u_max_new; } // (s_min / s_max stay the initial ones, like the reference's)
+   }
+};
+
+// One SSP-RK3 step u -> y1 -> y2 -> u of the one-kernel stage (rmh_stage_fused): the stage times and combinations of
+// RK3SSPSolver::Step; input and output vectors of a stage differ (y_out may alias x_base).  tok_u names the element extrema of u
+// left by the stage that wrote it (rmh_stage_fused_chain).
+// With vb_du (-vb) the kernel also hands out the limited rate, no tokens are used, and the granular kernels form the dof bounds of
+// the stage input for the check of remhos.cpp:1833-1837 (the LO rate never leaves the kernel: its check, :1824-1828, is the granular
+// sequence's -- rmhd_config.fused = 0).
+void fused_step(ParFiniteElementSpace &pfes, DofInfo &dofs, Vector &u, Vector &y1, Vector &y2, double &t, double dt_real,
+                unsigned long long &tok_u, Vector *vb_du)
+{
+   rmh_ctx *ctx = pfes.Ctx();
+   const int ne = pfes.GetNE();
+   Vector *const x[4] = {&u, &y1, &y2, &u};
+   unsigned long long tok = tok_u;
+   for (int i = 0; i < 3; i++)
+   {
+      const RK3SSPStage &st = RK3SSP[i];
+      const Vector &in = *x[i];
+      const double *xb = (i == 0) ? nullptr : u.Read();
+      RMH_CALL(rmh_setup(ctx, t + st.c * dt_real));
+      if (!vb_du)
+      {
+         RMH_CALL(rmh_stage_fused_chain(ctx, in.Read(), dt_real, xb, st.a, st.b, dt_real, x[i + 1]->Write(), nullptr, 0, ne, 1, tok,
+                                        (i == 2) ? &tok_u : &tok));
+         continue;
+      }
+      RMH_CALL(rmh_stage_fused_chain(ctx, in.Read(), dt_real, xb, st.a, st.b, dt_real, x[i + 1]->Write(), vb_du->Write(), 0, ne, 1, 0, nullptr));
+      dofs.ComputeElementsMinMax(in, dofs.xe_min, dofs.xe_max);
+      dofs.ComputeBounds(dofs.xe_min, dofs.xe_max, dofs.xi_min, dofs.xi_max);
+      check_violation(pfes, in, dt_real, *vb_du, dofs.xi_min, dofs.xi_max, "LimitMult FCT solution u", 1e-12, nullptr);
+   }
+   if (vb_du) { tok_u = 0; }
+   t += dt_real;
+}
+
+// Everything of one block's run that lives on the device.  rmhd_run_rank declares it AFTER the holder of the context, so every
+// Vector, DofInfo, solver and the AdvectionOperator here is destroyed BEFORE rmh_destroy; the members are declared in the order
+// the run creates them.
+struct BlockRun
+{
+   const rmhd_config &cfg; const CaseConfig &cc; const CaseData &cd;
+   rmh_ctx *const ctx;
+   Reduce reduce;
+   const int vsize;
+   const bool ps, vb, dtc;
+   ParFiniteElementSpace pfes; DofInfo dofs; Solvers solvers; AdvectionOperator adv; std::unique_ptr<MonolithicSolver> mono_solver;
+   Vector S, u; // Primary scalar field is u; for product remap we also evolve us (remhos.cpp:875-904): S = [u | us]
+   std::vector<double> h_u, h_m, h_us;
+   Vector masses;
+   double mass0 = 0.0; long double mass0_us_acc = 0.0L;
+   StepClock clock;
+   std::chrono::steady_clock::time_point w0, w1;
+
+   BlockRun(const rmhd_config &cfg_, const CaseConfig &cc_, const CaseData &cd_, rmh_ctx *ctx_, bool reduce_over_ranks);
+   void run();
+   void report(rmhd_result *res, double *u_final, double *us_final);
+};
+
+BlockRun::BlockRun(const rmhd_config &cfg_, const CaseConfig &cc_, const CaseData &cd_, rmh_ctx *ctx_, bool reduce_over_ranks)
+   : cfg(cfg_), cc(cc_), cd(cd_), ctx(ctx_), reduce{reduce_over_ranks ? ctx_ : nullptr, true}, vsize(cd_.ne_owned * cd_.ndof),
+     ps(cfg_.ps != 0), vb(cfg_.verify_bounds != 0), dtc(cfg_.dt_control != 0),
+     pfes(ctx_, cd_.ne_owned, cd_.ndof, (long long)cd_.ne_global * cd_.ndof, cd_.ne_ghost > 0), dofs(pfes),
+     solvers(make_solvers(cfg_, cc_, cd_, pfes)),
+     adv(pfes, dofs, solvers.ho.get(), solvers.lo.get(), solvers.fct.get(),
+         (ps || solvers.ode_type > 10) && cfg_.fused != 0 && cc_.lo_type == 5, ps),
+     mono_solver(make_mono_solver(cfg_, cc_, cd_, pfes, dofs)), S((ps ? 2 : 1) * vsize), u(S.ReadWrite(), vsize), h_u(vsize),
+     h_m(vsize), h_us(ps ? vsize : 0), masses(vsize)
+{
+   adv.mono_solver = mono_solver.get();
+   adv.verify_bounds = solvers.fct->verify_bounds = vb; // remhos.cpp:1115-1116
+   u.CopyFromHost(cd.u0.data());
+   if (ps)
+   {
+      // s = s0 where the element is active (BoolFunctionCoefficient on ComputeBoolIndicators(u), remhos.cpp:890-894),
+      // us = u * s node by node ("we don't target conservation at initialization", :899-900)
+      for (int e = 0; e < cd.ne_owned; e++)
+      {
+         bool active = false;
+         for (int i = 0; i < cd.ndof; i++) { active = active || cd.u0[(size_t)e * cd.ndof + i] > 1e-12; } // EMPTY_ZONE_TOL
+         for (int i = 0; i < cd.ndof; i++)
+         {
+            const size_t k = (size_t)e * cd.ndof + i;
+            h_us[k] = cd.u0[k] * (active ? cd.s0[k] : 0.0);
+         }
+      }
+      Vector us(S.ReadWrite() + vsize, vsize);
+      us.CopyFromHost(h_us.data());
+   }
+   // initial mass (remhos.cpp:1073-1076)
+   RMH_CALL(rmh_compute_lumped_mass(ctx, 0.0, masses.Write()));
+   masses.CopyToHost(h_m.data());
+   // (sums of ~1e7 terms: accumulated in extended precision so that the printed mass carries no summation error of its
+   // own -- the conservation claims are at the 1e-12 level)
+   long double mass0_acc = 0.0L;
+   for (int i = 0; i < vsize; i++) { mass0_acc += (long double)h_m[i] * cd.u0[i]; }
+   mass0 = reduce((double)mass0_acc, 0);
+   for (int i = 0; i < (ps ? vsize : 0); i++) { mass0_us_acc += (long double)h_m[i] * h_us[i]; } // remhos.cpp:1077-1081
+   // Print the starting mesh and initial condition (remhos.cpp:1015-1030)
+   if (cfg.save)
+   {
+      const std::string e = save_mfem(cd, 0.0, cd.u0.data(), "meshHO_init.mesh", "sltn_init.gf");
+      RMH_VERIFY(e.empty(), e.c_str());
+   }
+   clock.dt = cd.dt; clock.max_steps = cc.max_steps;
+   clock.t_final = cd.exec_mode == 1 ? 1.0 : cc.t_final; // For remap, the pseudo-time always evolves from 0 to 1 (remhos.cpp:1128-1134)
+   adv.SetTime(clock.t);
+   solvers.ode->Init(adv);
+}
+
+void BlockRun::run()
+{
+   const bool fused = solvers.fused;
+   HIP_CALL(hipDeviceSynchronize());
+   w0 = std::chrono::steady_clock::now();
+   Vector y1(fused ? vsize : 0), y2(fused ? vsize : 0);
+   unsigned long long tok_u = 0;
+   Vector Sold(dtc ? vsize : 0);
+   Vector vb_du(vb && fused ? vsize : 0);
+   std::unique_ptr<VbMonitor> monitor;
+   if (vb) { monitor.reset(new VbMonitor(pfes, dofs, reduce, ps, cc.problem)); monitor->start(S); }
+   bool done = false;
+   while (!done)
+   {
+      if (vb) { monitor->check(S); }
+      double dt_real = clock.next_dt();
+      // This also resets the time step estimate when automatic dt is on (remhos.cpp:1150-1152)
+      adv.SetDt(dt_real);
+      if (dtc) { adv.ResetTimeStepRatio(); Sold = u; }
+      if (fused) { fused_step(pfes, dofs, u, y1, y2, clock.t, dt_real, tok_u, vb ? &vb_du : nullptr); }
+      else { solvers.ode->Step(S, clock.t, dt_real); }
+      clock.count_step();
+      // remhos.cpp:1178-1197; the estimate is the minimum over the ranks of a partition (MPI_Allreduce(MIN),
+      // remhos.cpp:1993): every rank takes the same accept / repeat decision, hence issues the same exchanges
+      if (dtc && !clock.accept(reduce(adv.GetTimeStepRatio(), 1), dt_real))
+      {
+         // Repeat with the proper time step.
+         u = Sold;
+         tok_u = 0; // (u is no longer the output of the last stage)
+         RMH_VERIFY(!clock.crashed(), "The time step crashed!");
+         continue;
+      }
+      done = clock.done();
+   }
+   HIP_CALL(hipDeviceSynchronize());
+   w1 = std::chrono::steady_clock::now();
+}
+
+void BlockRun::report(rmhd_result *res, double *u_final, double *us_final)
+{
+   const double t = clock.t;
+   // final mass: remap uses the lumped mass at the final position (remhos.cpp:1382-1413)
+   if (cd.exec_mode == 1) { RMH_CALL(rmh_compute_lumped_mass(ctx, t, masses.Write())); masses.CopyToHost(h_m.data()); }
+   u.CopyToHost(h_u.data());
+   // Print the final mesh and solution (remhos.cpp:1365-1380)
+   if (cfg.save)
+   {
+      const std::string e = save_mfem(cd, t, h_u.data(), "meshHO_final.mesh", "sltn_final.gf");
+      RMH_VERIFY(e.empty(), e.c_str());
+   }
+   long double mass_acc = 0.0L;
+   double umax = -INFINITY;
+   for (int i = 0; i < vsize; i++) { mass_acc += (long double)h_m[i] * h_u[i]; umax = std::fmax(umax, h_u[i]); }
+   const double mass = reduce((double)mass_acc, 0);
+   umax = reduce(umax, 2);
+   if (u_final) { std::copy(h_u.begin(), h_u.end(), u_final); }
+   // Compute errors, if the exact solution is known (remhos.cpp:1438-1470)
+   double es[3];
+   if (lp_error_sums(cd, cc.problem, t, h_u.data(), es).empty())
+   {
+      res->has_errors = 1;
+      res->err_l1 = reduce(es[0], 0); res->err_l2 = std::sqrt(reduce(es[1], 0)); res->err_linf = reduce(es[2], 2);
+   }
+   if (ps)
+   {
+      // remhos.cpp:1404, 1416-1434: mass of us with the same lumped masses; max of the ratio s = us / u
+      Vector us(S.ReadWrite() + vsize, vsize), s_fin(vsize);
+      us.CopyToHost(h_us.data());
+      if (us_final) { std::copy(h_us.begin(), h_us.end(), us_final); }
+      long double acc = 0.0L;
+      for (int i = 0; i < vsize; i++) { acc += (long double)h_m[i] * h_us[i]; }
+      bool *flags = nullptr;
+      HIP_CALL(hipMalloc((void **)&flags, (size_t)cd.ne_owned + vsize));
+      Array<bool> el(flags, cd.ne_owned), dfl(flags + cd.ne_owned, vsize);
+      ComputeRatio(pfes, us, u, s_fin, el, dfl);
+      std::vector<double> h_s(vsize);
+      s_fin.CopyToHost(h_s.data());
+      (void)hipFree(flags);
+      double smax = -INFINITY;
+      for (int i = 0; i < vsize; i++) { smax = std::fmax(smax, h_s[i]); }
+      res->final_mass_us = reduce((double)acc, 0);
+      res->mass0_us = reduce((double)mass0_us_acc, 0);
+      res->mass_loss_us = std::fabs(res->mass0_us - res->final_mass_us);
+      res->s_max = reduce(smax, 2);
+   }
+   adv.Timer().Update(ctx); const TimingData &T = adv.Timer();
+   const double sw[4] = {T.sw_rhs, T.sw_L2inv, T.sw_LO, T.sw_FCT};
+   int it = 0; rmh_last_cg_iters(ctx, &it);
+   const int stages = solvers.stages_per_step * clock.ti_total;
+   fill_result_tail(res, mass0, mass, umax, clock, solvers.stages_per_step, pfes.GlobalVSize(), stages,
+                    sw, std::chrono::duration<double>(w1 - w0).count(), it);
+}
 } // namespace
+
+extern "C" int rmhd_run(const rmhd_config *cfg, rmhd_result *res) { return rmhd_run_rank(cfg, nullptr, 0, res, nullptr, nullptr); }
+
+extern "C" int rmhd_run_state(const rmhd_config *cfg, rmhd_result *res, double *u_final, double *us_final) { return rmhd_run_rank(cfg, nullptr, 0, res, u_final, us_final); }
+
+extern "C" int rmhd_run_rank(const rmhd_config *cfg_in, const char *comm_id_file, int device, rmhd_result *res, double *u_final,
+                             double *us_final)
+{
+   if (!cfg_in || !res) { return refuse("null argument"); }
+   std::memset(res, 0, sizeof(*res));
+   if (!(comm_id_file && comm_id_file[0])) { comm_id_file = nullptr; }
+   const Validated v = validate_config(*cfg_in, false, comm_id_file != nullptr);
+   if (!v.refusal.empty()) { return refuse(v.refusal); }
+   const rmhd_config &cfg = v.cfg;
+   const CaseConfig cc = to_config(cfg);
+   CaseData cd;
+   std::string err = build_case(cc, cd);
+   if (err.empty()) { err = check_case(cfg, cc, cd, false); }
+   if (!err.empty()) { return refuse(err); }
+   // Destruction runs bottom-up: `run` (every Vector, DofInfo, solver and the AdvectionOperator) goes before `ctx` (rmh_destroy),
+   // also on the refusals that find the context already open.
+   CtxPtr ctx;
+   bool reduce_over_ranks = false;
+   err = open_context(cfg, cc, cd, comm_id_file, device, ctx, reduce_over_ranks);
+   if (!err.empty()) { return refuse(err); }
+   BlockRun run(cfg, cc, cd, ctx.get(), reduce_over_ranks);
+   run.run();
+   run.report(res, u_final, us_final);
+   return 0;
+}
 
 extern "C" int rmhd_axpby(double a, const double *x, double b, const double *y, double *z, long long n, void *stream)
 {
@@ -1301,215 +1338,178 @@ extern "C" int rmhd_id_file_exchange(const char *path, int writer, char id[128])
    return 0;
 }
 
-extern "C" int rmhd_run_partitioned(const rmhd_config *cfg, const char *comm_id_file, int device, rmhd_result *res)
+// ---- box-partitioned runs: the time loop of remhos() (remhos.cpp:1146-1330) over the blocks of a ParMesh-like
+// partition, one fused kernel per RK stage and block, one neighbour exchange per stage (rmh_exchange_begin / _end) ----
+namespace
 {
-   if (!cfg || !res) { g_driver_error = "null argument"; return -1; }
-   CaseConfig cc0 = to_config(*cfg);
-   const int nranks = cc0.px * cc0.py * cc0.pz;
-   const bool rccl = comm_id_file && comm_id_file[0];
-   if (is_segment_mesh(cfg) && check_dim1(cfg, true) != 0) { return -1; }
-   if (is_file_mesh(cfg) && check_unstructured(cfg, true) != 0) { return -1; }
-   if (check_mono_type(cfg, true) != 0) { return -1; }
-   if (check_fct_type(cfg, true) != 0) { return -1; }
-   if (!cfg->fused) { g_driver_error = "rmhd_run_partitioned runs the one-kernel stage (fused = 1)"; return -1; }
-   std::vector<Block> blocks(rccl ? 1 : nranks);
-   auto cleanup = [&]()
+// A failing rmh_* / HIP call of the functions below: the call and its reason into the error, -1 to the caller
+#define RMHD_TRY(expr) do { if ((expr) != 0) { return refuse(std::string(#expr) + ": " + rmh_last_error()); } } while (0)
+#define RMHD_HIP(expr) do { if ((expr) != hipSuccess) { return refuse(#expr); } } while (0)
+
+struct Block
+{
+   CaseData cd;
+   rmh_ctx *ctx = nullptr;
+   double *x = nullptr, *y1 = nullptr, *y2 = nullptr, *xold = nullptr, *m = nullptr;
+   int vsize = 0;
+   unsigned long long tok = 0; // token of the extrema of the vector the next stage reads (rmh_stage_fused_chain)
+   hipStream_t stream = nullptr; // the context's stream: a non-blocking one, so that the exchange stream overlaps it
+
+   Block() {}
+   Block(const Block &) = delete; Block &operator=(const Block &) = delete;
+   // the buffers, then the context, then the stream the context ran on
+   ~Block()
    {
-      for (Block &b : blocks)
-      {
-         (void)hipFree(b.x); (void)hipFree(b.y1); (void)hipFree(b.y2); (void)hipFree(b.xold); (void)hipFree(b.m);
-         if (b.ctx) { rmh_destroy(b.ctx); }
-         if (b.stream) { (void)hipStreamDestroy(b.stream); }
-      }
-   };
-#define RMHD_TRY(expr)                                                          \
-   do {                                                                         \
-      if ((expr) != 0) { g_driver_error = std::string(#expr) + ": " + rmh_last_error(); cleanup(); return -1; } \
-   } while (0)
-#define RMHD_HIP(expr)                                                          \
-   do {                                                                         \
-      if ((expr) != hipSuccess) { g_driver_error = #expr; cleanup(); return -1; } \
-   } while (0)
-   // ---- set-up of every block this process owns ------------------------------------------------------------------
-   for (size_t k = 0; k < blocks.size(); k++)
-   {
-      Block &b = blocks[k];
-      CaseConfig cc = cc0;
-      cc.rank = rccl ? cc0.rank : (int)k;
-      const std::string err = build_case(cc, b.cd);
-      if (!err.empty()) { g_driver_error = err; cleanup(); return -1; }
-      rmh_layout L;
-      if (b.cd.dim != 3) { g_driver_error = "the partitioned stage loop is for the 3-D cases"; cleanup(); return -1; }
-      L.dim = 3; L.order = b.cd.order; L.mesh_order = 2; L.exec_mode = b.cd.exec_mode;
-      L.ne_owned = b.cd.ne_owned; L.ne_ghost = b.cd.ne_ghost;
-      L.x0 = b.cd.x0.data(); L.vel = b.cd.vel.data(); L.face_nbr = b.cd.face_nbr.data(); L.stencil27 = b.cd.stencil27.data();
-      L.subcell_vel = b.cd.subcell_vel.empty() ? nullptr : b.cd.subcell_vel.data();
-      L.device = device;
-      RMHD_TRY(rmh_create(&L, &b.ctx));
-      {
-         // RMH_COMM_CUS = k: the stage kernels leave k compute units to the exchange stream (rmh_stream_create_reserving; only
-         // where RCCL kernels run beside them -- same-process blocks exchange by device copies)
-         const char *ecu = std::getenv("RMH_COMM_CUS");
-         const int kcu = (rccl && ecu) ? std::atoi(ecu) : 0;
-         void *sv = nullptr;
-         RMHD_TRY(rmh_stream_create_reserving(device, kcu > 0 ? kcu : 0, &sv));
-         b.stream = (hipStream_t)sv;
-      }
-      RMHD_TRY(rmh_set_stream(b.ctx, b.stream));
-      RMHD_TRY(rmh_set_lo_type(b.ctx, cc.lo_type));
-      RMHD_TRY(rmh_set_bounds_type(b.ctx, cfg->bounds_type));
-      if (cfg->dt_control) { RMHD_TRY(rmh_set_dt_control(b.ctx, 1)); }
-      if (cfg->ho_type == 2) { RMHD_TRY(rmh_set_mass_tol(b.ctx, 1e-12, 0.0, 500)); }
-      else if (cfg->pa)
-      {
-         // LocalInverseHOSolver on a partially assembled M (remhos_ho.cpp:77-81): DGMassInverse's rule, completed
-         RMHD_TRY(rmh_set_mass_tol(b.ctx, 0.0, 1e-8, 100));
-         RMHD_TRY(rmh_set_mass_completion(b.ctx, 1, 1));
-      }
-      b.vsize = b.cd.ne_owned * b.cd.ndof;
-      const size_t bytes = sizeof(double) * (size_t)b.vsize;
-      RMHD_HIP(hipMalloc((void **)&b.x, bytes));
-      RMHD_HIP(hipMalloc((void **)&b.y1, bytes));
-      RMHD_HIP(hipMalloc((void **)&b.y2, bytes));
-      RMHD_HIP(hipMalloc((void **)&b.m, bytes));
-      if (cfg->dt_control) { RMHD_HIP(hipMalloc((void **)&b.xold, bytes)); }
-      RMHD_HIP(hipMemcpy(b.x, b.cd.u0.data(), bytes, hipMemcpyHostToDevice));
-      // exchange plan from the case builder's halo lists; compact records unless a block is one element thin
-      const int np = (int)b.cd.peers.size();
-      std::vector<int> prank(np), scount(np), rfirst(np), rcount(np);
-      std::vector<const int *> selems(np);
-      for (int j = 0; j < np; j++)
-      {
-         const Peer &pr = b.cd.peers[j];
-         prank[j] = pr.rank;
-         scount[j] = (int)pr.send_elems.size();
-         selems[j] = pr.send_elems.data();
-         rfirst[j] = pr.recv_slots.empty() ? 0 : pr.recv_slots.front();
-         rcount[j] = (int)pr.recv_slots.size();
-      }
-      rmh_exchange_desc d = {np, prank.data(), scount.data(), selems.data(), rfirst.data(), rcount.data()};
-      bool thin = false;
-      const int P3[3] = {cc.px, cc.py, cc.pz};
-      for (int dd = 0; dd < 3; dd++) { thin = thin || (P3[dd] > 1 && b.cd.n[dd] / P3[dd] < 2); }
-      RMHD_TRY(rmh_exchange_setup(b.ctx, &d, thin ? 0 : 1));
+      (void)hipFree(x); (void)hipFree(y1); (void)hipFree(y2); (void)hipFree(xold); (void)hipFree(m);
+      if (ctx) { rmh_destroy(ctx); }
+      if (stream) { (void)hipStreamDestroy(stream); }
    }
-   if (rccl)
+};
+
+// Set-up of one block this process owns: case, context on a stream of its own, the options of the one-kernel stage, buffers,
+// exchange plan
+int setup_block(Block &b, const rmhd_config *cfg, const CaseConfig &cc, int device, bool rccl)
+{
+   std::string err = build_case(cc, b.cd);
+   if (err.empty()) { err = check_case(*cfg, cc, b.cd, true); }
+   if (!err.empty()) { return refuse(err); }
+   const rmh_layout L = make_layout(b.cd, device);
+   RMHD_TRY(rmh_create(&L, &b.ctx));
+   // RMH_COMM_CUS = k: the stage kernels leave k compute units to the exchange stream (rmh_stream_create_reserving; only
+   // where RCCL kernels run beside them -- same-process blocks exchange by device copies)
+   const char *ecu = std::getenv("RMH_COMM_CUS");
+   const int kcu = (rccl && ecu) ? std::atoi(ecu) : 0;
+   void *sv = nullptr;
+   RMHD_TRY(rmh_stream_create_reserving(device, kcu > 0 ? kcu : 0, &sv));
+   b.stream = (hipStream_t)sv;
+   RMHD_TRY(rmh_set_stream(b.ctx, b.stream));
+   RMHD_TRY(rmh_set_lo_type(b.ctx, cc.lo_type));
+   RMHD_TRY(rmh_set_bounds_type(b.ctx, cfg->bounds_type));
+   if (cfg->dt_control) { RMHD_TRY(rmh_set_dt_control(b.ctx, 1)); }
+   if (cfg->ho_type == 2) { RMHD_TRY(rmh_set_mass_tol(b.ctx, 1e-12, 0.0, 500)); }
+   else if (cfg->pa)
    {
-      char id[128];
-      if (cc0.rank == 0)
-      {
-         std::remove(comm_id_file); // (a stale record: see read_or_write_id)
-         RMHD_TRY(rmh_comm_unique_id(id));
-      }
-      if (!read_or_write_id(comm_id_file, cc0.rank == 0, id)) { g_driver_error = "cannot exchange the RCCL unique id through the file"; cleanup(); return -1; }
-      RMHD_TRY(rmh_comm_init(blocks[0].ctx, id, nranks, cc0.rank));
-      if (cc0.rank == 0) { std::remove(comm_id_file); } // (every rank has read it: ncclCommInitRank is collective)
+      // LocalInverseHOSolver on a partially assembled M (remhos_ho.cpp:77-81): DGMassInverse's rule, completed
+      RMHD_TRY(rmh_set_mass_tol(b.ctx, 0.0, 1e-8, 100));
+      RMHD_TRY(rmh_set_mass_completion(b.ctx, 1, 1));
    }
-   else
+   b.vsize = b.cd.ne_owned * b.cd.ndof;
+   const size_t bytes = sizeof(double) * (size_t)b.vsize;
+   RMHD_HIP(hipMalloc((void **)&b.x, bytes));
+   RMHD_HIP(hipMalloc((void **)&b.y1, bytes));
+   RMHD_HIP(hipMalloc((void **)&b.y2, bytes));
+   RMHD_HIP(hipMalloc((void **)&b.m, bytes));
+   if (cfg->dt_control) { RMHD_HIP(hipMalloc((void **)&b.xold, bytes)); }
+   RMHD_HIP(hipMemcpy(b.x, b.cd.u0.data(), bytes, hipMemcpyHostToDevice));
+   if (ExchangePlan(b.cd, cc).setup(b.ctx) != 0) { return refuse(std::string("rmh_exchange_setup: ") + rmh_last_error()); }
+   return 0;
+}
+
+// The transport between the blocks: RCCL between processes (one block each), device copies between the blocks of this one
+int connect_blocks(std::vector<Block> &blocks, const char *comm_id_file, int nranks, int rank)
+{
+   if (comm_id_file)
    {
-      for (int r = 0; r < nranks; r++)
+      const char *failed = rccl_rendezvous(blocks[0].ctx, comm_id_file, nranks, rank);
+      if (failed == ID_FILE_FAILED) { return refuse(failed); }
+      return failed ? refuse(std::string(failed) + ": " + rmh_last_error()) : 0;
+   }
+   for (int r = 0; r < nranks; r++)
+   {
+      for (size_t j = 0; j < blocks[r].cd.peers.size(); j++)
       {
-         for (size_t j = 0; j < blocks[r].cd.peers.size(); j++)
-         {
-            const int q = blocks[r].cd.peers[j].rank;
-            if (q < r) { continue; } // (each pair once; a block may be its own neighbour's neighbour only through q != r)
-            int jq = -1;
-            for (size_t i = 0; i < blocks[q].cd.peers.size(); i++) { if (blocks[q].cd.peers[i].rank == r) { jq = (int)i; } }
-            if (jq < 0) { g_driver_error = "halo lists of two blocks do not mirror each other"; cleanup(); return -1; }
-            RMHD_TRY(rmh_comm_connect_local(blocks[r].ctx, (int)j, blocks[q].ctx, jq));
-         }
+         const int q = blocks[r].cd.peers[j].rank;
+         if (q < r) { continue; } // (each pair once; a block may be its own neighbour's neighbour only through q != r)
+         int jq = -1;
+         for (size_t i = 0; i < blocks[q].cd.peers.size(); i++) { if (blocks[q].cd.peers[i].rank == r) { jq = (int)i; } }
+         if (jq < 0) { return refuse("halo lists of two blocks do not mirror each other"); }
+         RMHD_TRY(rmh_comm_connect_local(blocks[r].ctx, (int)j, blocks[q].ctx, jq));
       }
    }
-   bool reduce_failed = false;
-   auto reduce = [&](double v, int op) -> double
+   return 0;
+}
+
+// Mass and maximum of x over all blocks and ranks at time t; with `errors`, also the sums of the error norms where the exact
+// solution is known (remhos.cpp:1438-1470; MPI-reduced like ComputeLpError): errors[3] = has any, then sum |e| w, sum e^2 w, max |e|
+bool mass_and_max(std::vector<Block> &blocks, Reduce &reduce, int problem, double t, double &mass, double &umax, double *errors)
+{
+   mass = 0.0; umax = -INFINITY;
+   for (Block &b : blocks)
    {
-      // over the blocks of this process, then over the ranks of the communicator
-      if (rccl) { if (rmh_allreduce(blocks[0].ctx, &v, 1, op) != 0) { reduce_failed = true; } }
-      return v;
-   };
-   bool want_errors = false, have_errors = false;
-   double err_sums[3] = {0, 0, 0};
-   auto mass_and_max = [&](double t, double &mass, double &umax) -> bool
-   {
-      mass = 0.0; umax = -INFINITY;
-      for (Block &b : blocks)
+      if (rmh_compute_lumped_mass(b.ctx, b.cd.exec_mode == 1 ? t : 0.0, b.m) != 0) { return false; }
+      if (hipStreamSynchronize(b.stream) != hipSuccess) { return false; } // (a non-blocking stream: the copies below do not wait for it)
+      std::vector<double> hm(b.vsize), hu(b.vsize);
+      if (hipMemcpy(hm.data(), b.m, sizeof(double) * b.vsize, hipMemcpyDeviceToHost) != hipSuccess) { return false; }
+      if (hipMemcpy(hu.data(), b.x, sizeof(double) * b.vsize, hipMemcpyDeviceToHost) != hipSuccess) { return false; }
+      long double acc = 0.0L; // (extended precision: see BlockRun)
+      for (int i = 0; i < b.vsize; i++) { acc += (long double)hm[i] * hu[i]; umax = std::fmax(umax, hu[i]); }
+      mass += (double)acc;
+      double es[3];
+      if (errors && lp_error_sums(b.cd, problem, t, hu.data(), es).empty())
       {
-         if (rmh_compute_lumped_mass(b.ctx, b.cd.exec_mode == 1 ? t : 0.0, b.m) != 0) { return false; }
-         if (hipStreamSynchronize(b.stream) != hipSuccess) { return false; } // (a non-blocking stream: the copies below do not wait for it)
-         std::vector<double> hm(b.vsize), hu(b.vsize);
-         if (hipMemcpy(hm.data(), b.m, sizeof(double) * b.vsize, hipMemcpyDeviceToHost) != hipSuccess) { return false; }
-         if (hipMemcpy(hu.data(), b.x, sizeof(double) * b.vsize, hipMemcpyDeviceToHost) != hipSuccess) { return false; }
-         long double acc = 0.0L; // (extended precision: see rmhd_run)
-         for (int i = 0; i < b.vsize; i++) { acc += (long double)hm[i] * hu[i]; umax = std::fmax(umax, hu[i]); }
-         mass += (double)acc;
-         double es[3];
-         if (want_errors && lp_error_sums(b.cd, cc0.problem, t, hu.data(), es).empty())
-         {
-            have_errors = true;
-            err_sums[0] += es[0]; err_sums[1] += es[1]; err_sums[2] = std::fmax(err_sums[2], es[2]);
-         }
+         errors[3] = 1.0; errors[0] += es[0]; errors[1] += es[1]; errors[2] = std::fmax(errors[2], es[2]);
       }
-      mass = reduce(mass, 0);  // MPI_Allreduce SUM, remhos.cpp:1412
-      umax = reduce(umax, 2);  // MPI_Allreduce MAX, remhos.cpp:1415
-      return true;
-   };
-   double mass0 = 0, umax0 = 0;
-   if (!mass_and_max(0.0, mass0, umax0)) { g_driver_error = "initial mass"; cleanup(); return -1; }
-   // ---- time loop ----------------------------------------------------------------------------------------------
-   const double t_final = blocks[0].cd.exec_mode == 1 ? 1.0 : cc0.t_final;
-   double dt = blocks[0].cd.dt, t = 0.0;
-   int ti = 0, ti_total = 0, repeats = 0;
-   bool done = false;
-   // TimingData buckets: HIP events around the launches of every `timer_every`-th step (default 4; RMH_DRIVER_TIMERS = k, 0 =
-   // never), scaled to all steps in the report.  Events around EVERY launch cost the 48^3-element blocks of an 8-rank strong run
-   // 8 % (measured with all eight blocks on one GPU: 14.8 k -> 16.1 k MDOFs*stage/s without them); the wall clock is exact.
-   const char *tenv = std::getenv("RMH_DRIVER_TIMERS");
-   const int timer_every = tenv ? std::max(0, std::atoi(tenv)) : 4;
-   int timed_steps = 0, counted_steps = 0;
-   for (Block &b : blocks) { RMHD_TRY(rmh_enable_timers(b.ctx, 0)); }
-   RMHD_HIP(hipDeviceSynchronize());
-   auto w0 = std::chrono::steady_clock::now();
+   }
+   mass = reduce(mass, 0);  // MPI_Allreduce SUM, remhos.cpp:1412
+   umax = reduce(umax, 2);  // MPI_Allreduce MAX, remhos.cpp:1415
+   return true;
+}
+
+// One RK stage of all blocks: post every exchange, run the elements that reach no ghost while the messages are
+// in flight, complete the exchanges, run the halo-dependent shells
+bool stage_of_all_blocks(std::vector<Block> &blocks, int which, double t, double dt_real)
+{
+   const RK3SSPStage &st = RK3SSP[which];
+   const double ts = t + st.c * dt_real;
+   auto in = [&](Block &b) { return which == 0 ? b.x : (which == 1 ? b.y1 : b.y2); };
+   auto out = [&](Block &b) { return which == 0 ? b.y1 : (which == 1 ? b.y2 : b.x); };
+   for (Block &b : blocks) { if (rmh_exchange_begin(b.ctx, in(b)) != 0) { return false; } }
+   for (Block &b : blocks)
+   {
+      if (rmh_setup(b.ctx, ts) != 0) { return false; }
+      if (rmh_stage_fused_chain(b.ctx, in(b), dt_real, which == 0 ? nullptr : b.x, st.a, st.b, dt_real, out(b), nullptr,
+                                b.cd.ne_halo, b.cd.ne_owned, 0, b.tok, nullptr) != 0) { return false; }
+   }
+   for (Block &b : blocks) { if (rmh_exchange_end(b.ctx) != 0) { return false; } }
+   for (Block &b : blocks)
+   {
+      if (rmh_stage_fused_chain(b.ctx, in(b), dt_real, which == 0 ? nullptr : b.x, st.a, st.b, dt_real, out(b), nullptr, 0,
+                                b.cd.ne_halo, 1, b.tok, &b.tok) != 0) { return false; }
+   }
+   return true;
+}
+
+// TimingData buckets: HIP events around the launches of every `every`-th step (default 4; RMH_DRIVER_TIMERS = k, 0 =
+// never), scaled to all steps in the report.  Events around EVERY launch cost the 48^3-element blocks of an 8-rank strong run
+// 8 % (measured with all eight blocks on one GPU: 14.8 k -> 16.1 k MDOFs*stage/s without them); the wall clock is exact.
+struct TimerSampling
+{
+   int every = 4, timed_steps = 0, counted_steps = 0;
    int timed_from = 0; // steps taken before the stopwatches (re)started (rmhd_config.warmup_steps)
-   // one RK stage of all blocks: post every exchange, run the elements that reach no ghost while the messages are
-   // in flight, complete the exchanges, run the halo-dependent shells
-   auto stage = [&](int which, double ts, double dt_real, double ra, double rb) -> bool
-   {
-      auto in = [&](Block &b) { return which == 0 ? b.x : (which == 1 ? b.y1 : b.y2); };
-      auto out = [&](Block &b) { return which == 0 ? b.y1 : (which == 1 ? b.y2 : b.x); };
-      for (Block &b : blocks) { if (rmh_exchange_begin(b.ctx, in(b)) != 0) { return false; } }
-      for (Block &b : blocks)
-      {
-         if (rmh_setup(b.ctx, ts) != 0) { return false; }
-         if (rmh_stage_fused_chain(b.ctx, in(b), dt_real, which == 0 ? nullptr : b.x, ra, rb, dt_real, out(b), nullptr,
-                                   b.cd.ne_halo, b.cd.ne_owned, 0, b.tok, nullptr) != 0) { return false; }
-      }
-      for (Block &b : blocks) { if (rmh_exchange_end(b.ctx) != 0) { return false; } }
-      for (Block &b : blocks)
-      {
-         if (rmh_stage_fused_chain(b.ctx, in(b), dt_real, which == 0 ? nullptr : b.x, ra, rb, dt_real, out(b), nullptr, 0,
-                                   b.cd.ne_halo, 1, b.tok, &b.tok) != 0) { return false; }
-      }
-      return true;
-   };
+   std::chrono::steady_clock::time_point w0;
+};
+
+// The time loop: RK3SSPSolver::Step per step, -dtc with the estimate reduced over blocks and ranks
+int partitioned_loop(std::vector<Block> &blocks, const rmhd_config *cfg, Reduce &reduce, StepClock &clock, TimerSampling &ts)
+{
+   bool done = false;
    while (!done)
    {
-      if (cfg->warmup_steps > 0 && ti_total == cfg->warmup_steps)
+      if (cfg->warmup_steps > 0 && clock.ti_total == cfg->warmup_steps)
       {
          // the timed region starts here: everything before is finished on every rank (the reduction is the barrier)
          RMHD_HIP(hipDeviceSynchronize());
          (void)reduce(0.0, 0);
          for (Block &b : blocks) { RMHD_TRY(rmh_reset_timers(b.ctx)); }
-         timed_from = ti_total;
-         timed_steps = counted_steps = 0;
-         w0 = std::chrono::steady_clock::now();
+         ts.timed_from = clock.ti_total;
+         ts.timed_steps = ts.counted_steps = 0;
+         ts.w0 = std::chrono::steady_clock::now();
       }
-      {
-         const bool sample = timer_every > 0 && counted_steps % timer_every == 0;
-         for (Block &b : blocks) { RMHD_TRY(rmh_enable_timers(b.ctx, sample ? 1 : 0)); }
-         timed_steps += sample ? 1 : 0;
-         counted_steps++;
-      }
-      const double dt_real = std::min(dt, t_final - t);
+      const bool sample = ts.every > 0 && ts.counted_steps % ts.every == 0;
+      for (Block &b : blocks) { RMHD_TRY(rmh_enable_timers(b.ctx, sample ? 1 : 0)); }
+      ts.timed_steps += sample ? 1 : 0;
+      ts.counted_steps++;
+      const double dt_real = clock.next_dt();
       if (cfg->dt_control)
       {
          for (Block &b : blocks)
@@ -1519,53 +1519,73 @@ extern "C" int rmhd_run_partitioned(const rmhd_config *cfg, const char *comm_id_
          }
          RMHD_HIP(hipDeviceSynchronize());
       }
-      // RK3SSPSolver::Step: stage times t, t + dt, t + dt/2
-      if (!stage(0, t, dt_real, 0.0, 1.0) || !stage(1, t + dt_real, dt_real, 3. / 4, 1. / 4) ||
-          !stage(2, t + dt_real / 2, dt_real, 1. / 3, 2. / 3))
+      for (int which = 0; which < 3; which++)
       {
-         g_driver_error = std::string("stage: ") + rmh_last_error(); cleanup(); return -1;
+         if (!stage_of_all_blocks(blocks, which, clock.t, dt_real)) { return refuse(std::string("stage: ") + rmh_last_error()); }
       }
-      t += dt_real;
-      ti++;
-      ti_total++;
+      clock.t += dt_real;
+      clock.count_step();
       if (cfg->dt_control)
       {
          double est = INFINITY;
          for (Block &b : blocks) { double e = 0; RMHD_TRY(rmh_dt_estimate_get(b.ctx, &e)); est = std::fmin(est, e); }
          est = reduce(est, 1); // MPI_Allreduce MIN, remhos.cpp:1993
-         const double ratio = dt_real != 0. ? est / dt_real : 0.;
-         if (ratio < 1.)
+         if (!clock.accept(dt_real != 0. ? est / dt_real : 0., dt_real))
          {
-            ti--;
-            t -= dt_real;
             for (Block &b : blocks)
             {
                RMHD_HIP(hipMemcpyAsync(b.x, b.xold, sizeof(double) * b.vsize, hipMemcpyDeviceToDevice, b.stream));
                b.tok = 0; // (x is no longer the output of the last stage)
             }
             RMHD_HIP(hipDeviceSynchronize());
-            dt = 0.85 * dt;
-            repeats++;
-            if (dt < 1e-12) { g_driver_error = "The time step crashed!"; cleanup(); return -1; }
+            if (clock.crashed()) { return refuse("The time step crashed!"); }
             continue;
          }
-         else if (ratio > 1.25) { dt *= 1.02; }
       }
-      done = (t >= t_final - 1.e-8 * dt);
-      if (ti_total == cc0.max_steps) { done = true; }
+      done = clock.done();
    }
+   return 0;
+}
+} // namespace
+
+extern "C" int rmhd_run_partitioned(const rmhd_config *cfg_in, const char *comm_id_file, int device, rmhd_result *res)
+{
+   if (!cfg_in || !res) { return refuse("null argument"); }
+   if (!(comm_id_file && comm_id_file[0])) { comm_id_file = nullptr; }
+   const bool rccl = comm_id_file != nullptr;
+   const Validated v = validate_config(*cfg_in, true, rccl);
+   if (!v.refusal.empty()) { return refuse(v.refusal); }
+   const rmhd_config *cfg = &v.cfg;
+   const CaseConfig cc0 = to_config(*cfg);
+   const int nranks = cc0.px * cc0.py * cc0.pz;
+   // every block this process owns; a block frees its buffers, its context and its stream when `blocks` goes, on every return
+   std::vector<Block> blocks(rccl ? 1 : nranks);
+   for (size_t k = 0; k < blocks.size(); k++)
+   {
+      CaseConfig cc = cc0;
+      cc.rank = rccl ? cc0.rank : (int)k;
+      if (setup_block(blocks[k], cfg, cc, device, rccl) != 0) { return -1; }
+   }
+   if (connect_blocks(blocks, comm_id_file, nranks, cc0.rank) != 0) { return -1; }
+   Reduce reduce{rccl ? blocks[0].ctx : nullptr, false}; // over the blocks of this process, then over the ranks of the communicator
+   double mass0 = 0, umax0 = 0;
+   if (!mass_and_max(blocks, reduce, cc0.problem, 0.0, mass0, umax0, nullptr)) { return refuse("initial mass"); }
+   StepClock clock;
+   clock.dt = blocks[0].cd.dt; clock.max_steps = cc0.max_steps;
+   clock.t_final = blocks[0].cd.exec_mode == 1 ? 1.0 : cc0.t_final;
+   TimerSampling ts;
+   const char *tenv = std::getenv("RMH_DRIVER_TIMERS");
+   ts.every = tenv ? std::max(0, std::atoi(tenv)) : 4;
+   for (Block &b : blocks) { RMHD_TRY(rmh_enable_timers(b.ctx, 0)); }
+   RMHD_HIP(hipDeviceSynchronize());
+   ts.w0 = std::chrono::steady_clock::now();
+   if (partitioned_loop(blocks, cfg, reduce, clock, ts) != 0) { return -1; }
    RMHD_HIP(hipDeviceSynchronize());
    (void)reduce(0.0, 0); // (every rank has finished its last stage)
    const auto w1 = std::chrono::steady_clock::now();
-   double mass = 0, umax = 0;
-   want_errors = true; // (remhos.cpp:1438-1470; MPI-reduced like ComputeLpError)
-   if (!mass_and_max(t, mass, umax)) { g_driver_error = "final mass"; cleanup(); return -1; }
-   if (have_errors)
-   {
-      err_sums[0] = reduce(err_sums[0], 0);
-      err_sums[1] = reduce(err_sums[1], 0);
-      err_sums[2] = reduce(err_sums[2], 2);
-   }
+   double mass = 0, umax = 0, errors[4] = {0, 0, 0, 0};
+   if (!mass_and_max(blocks, reduce, cc0.problem, clock.t, mass, umax, errors)) { return refuse("final mass"); }
+   if (errors[3] != 0.) { errors[0] = reduce(errors[0], 0); errors[1] = reduce(errors[1], 0); errors[2] = reduce(errors[2], 2); }
    double tk = 0.0;
    int itmax = 0;
    for (Block &b : blocks)
@@ -1577,49 +1597,25 @@ extern "C" int rmhd_run_partitioned(const rmhd_config *cfg, const char *comm_id_
       rmh_last_cg_iters(b.ctx, &it);
       itmax = std::max(itmax, it);
    }
-   if (timed_steps > 0) { tk *= (double)counted_steps / timed_steps; } // (sampled steps -> all steps of the timed region)
+   if (ts.timed_steps > 0) { tk *= (double)ts.counted_steps / ts.timed_steps; } // (sampled steps -> all steps of the timed region)
    tk = reduce(tk, 2); // MPI_Reduce MAX of the stopwatches, remhos.cpp:1934
-   if (reduce_failed) { g_driver_error = std::string("rmh_allreduce: ") + rmh_last_error(); cleanup(); return -1; }
+   const double wall = reduce(std::chrono::duration<double>(w1 - ts.w0).count(), 2);
+   if (reduce.failed) { return refuse(std::string("rmh_allreduce: ") + rmh_last_error()); }
    std::memset(res, 0, sizeof(*res));
-   res->timer_every = timer_every;
-   res->timer_steps = timed_steps;
-   res->final_mass = mass;
-   res->max_value = umax;
-   res->mass0 = mass0;
-   res->mass_loss = std::fabs(mass0 - mass);
-   if (have_errors)
-   {
-      res->has_errors = 1;
-      res->err_l1 = err_sums[0];
-      res->err_l2 = std::sqrt(err_sums[1]);
-      res->err_linf = err_sums[2];
-   }
-   res->dt = dt;
-   res->t_end = t;
-   res->steps = ti;
-   res->stages = 3 * ti_total;
-   res->global_dofs = blocks[0].cd.ne_global * blocks[0].cd.ndof;
-   res->t_rhs = tk; // the whole stage is one kernel: everything is in the RHS bucket
-   res->t_total = tk;
-   res->timed_stages = 3 * (ti_total - timed_from);
+   res->timer_every = ts.every; res->timer_steps = ts.timed_steps;
+   if (errors[3] != 0.) { res->has_errors = 1; res->err_l1 = errors[0]; res->err_l2 = std::sqrt(errors[1]); res->err_linf = errors[2]; }
+   res->timed_stages = 3 * (clock.ti_total - ts.timed_from);
    res->n_peers = (int)blocks[0].cd.peers.size();
    res->transport = rccl ? 1 : (nranks > 1 ? 2 : 0);
    if (rccl) { (void)rmh_comm_count(blocks[0].ctx, &res->comm_ranks); }
-   {
-      long long sd = 0, gd = 0;
-      if (res->n_peers > 0) { (void)rmh_exchange_buffers(blocks[0].ctx, nullptr, &sd, nullptr, &gd); }
-      res->send_bytes_per_stage = 8 * sd;
-      res->recv_bytes_per_stage = 8 * gd;
-   }
-   const double dofs_steps = 1e-6 * (double)res->global_dofs * res->timed_stages;
-   res->fom_rhs = tk > 0 ? dofs_steps / tk : 0;
-   res->fom = res->fom_rhs;
-   res->wall = reduce(std::chrono::duration<double>(w1 - w0).count(), 2);
-   res->fom_wall = dofs_steps / res->wall;
-   res->cg_iters_max = itmax;
-   res->repeats = repeats;
-   cleanup();
+   long long sd = 0, gd = 0;
+   if (res->n_peers > 0) { (void)rmh_exchange_buffers(blocks[0].ctx, nullptr, &sd, nullptr, &gd); }
+   res->send_bytes_per_stage = 8 * sd; res->recv_bytes_per_stage = 8 * gd;
+   const double T[4] = {tk, 0., 0., 0.}; // the whole stage is one kernel: everything is in the RHS bucket
+   fill_result_tail(res, mass0, mass, umax, clock, 3, blocks[0].cd.ne_global * blocks[0].cd.ndof, res->timed_stages, T, wall, itmax);
    return 0;
+}
+
 #undef RMHD_TRY
 #undef RMHD_HIP
-}
+
